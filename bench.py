@@ -7,7 +7,7 @@ GPU).  A "step" is ONE pass of the hot path (one d2pc_process_device call)
 over a ring of 16 distinct synthetic 4K frames already resident in HBM
 (531 MB in, 2.0 GB out: larger than the 256 MiB Infinity Cache).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment starts the N
@@ -18,8 +18,13 @@ node, here one per GPU), relays rank 0's JSON line and exits with the child's
 code.  A rank whose WORLD_SIZE differs from --gpus fails.
 
 Prints ONE JSON line (rank 0) with `roofline` (algorithmic bytes / measured
-kernel time vs 8 TB/s HBM peak) and `cpu_baseline` (the oracle's single-thread
-restatement of the reference loop timed on this host, bounded sample).
+kernel time vs 8 TB/s HBM peak).  A plain run sets up, warms up, times the K
+steps and prints the line, nothing else.  `--full` adds the side measurements
+behind the timed region: device calibration, shader clock, sustained spread
+rounds, the 1-GPU variants, the host-path rates and `cpu_baseline` (the
+oracle's single-thread restatement of the reference loop timed on this host,
+bounded sample).  `--dump-outputs DIR` writes what the last timed step computed
+as .npy files (dump_outputs).
 """
 import argparse
 import json
@@ -152,6 +157,31 @@ class RingLaunch:
                                 b.counts.data_ptr() + f * 4, self.stream)
         if not self.fixed:
             self.pos = (self.pos + 1) % self.positions
+
+
+DUMP_SAMPLE_POINTS = 1 << 20   # 16 MB of float32 xyzw out of the step's 2-GB cloud
+DUMP_SEED = 0xD2C0D
+
+
+def dump_outputs(batch, out_dir, suffix=""):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as .npy files in `out_dir` --
+    counts.npy (float64 [frames]: points per frame) and the points of a fixed, seeded sample of positions below each
+    frame's count: points_sample.npy (float32 [S, 4]) and points_sample_at.npy (float64 [S, 2]: frame, position).
+    The sample depends only on the seed and the counts, so two builds that compute the same counts dump the same
+    positions.  Must run before anything else writes into the batch's output buffer."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    counts = batch.counts.cpu().numpy().astype(np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    frame = rng.integers(0, batch.n_frames, size=DUMP_SAMPLE_POINTS)
+    pos = np.floor(rng.random(size=DUMP_SAMPLE_POINTS) * counts[frame]).astype(np.int64)
+    keep = counts[frame] > 0
+    flat = np.sort(frame[keep] * batch.stride + pos[keep])   # ascending: frame-major, then position
+    pts = batch.points.view(-1, 4).index_select(0, torch.from_numpy(flat).to(batch.points.device)).cpu().numpy()
+    np.save(os.path.join(out_dir, f"counts{suffix}.npy"), counts.astype(np.float64))
+    np.save(os.path.join(out_dir, f"points_sample{suffix}.npy"), pts.astype(np.float32))
+    np.save(os.path.join(out_dir, f"points_sample_at{suffix}.npy"),
+            np.stack([flat // batch.stride, flat % batch.stride], axis=1).astype(np.float64))
 
 
 def algorithmic_bytes(batch, n_points, with_index):
@@ -579,14 +609,20 @@ def main():
     ap.add_argument("--heat-ms", type=float, default=60.0,
                     help="time floor of the warm-up: after the W warm-up steps the same launch is repeated, untimed, until "
                          "this much device time has passed (0 = warm up by count only)")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement behind the timed region: device calibration, shader clock, "
+                         "spread rounds, the 1-GPU variants, the host-path rates and the CPU baselines (the --no-* "
+                         "switches below drop parts of it); a plain run times the headline only")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the 1-GPU variants")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the device calibration and the spread rounds behind the timed region, so that a rocprofv3 "
-                         "--stats run sees the contract's launches only (its per-kernel average is then the line's)")
+                    help="with --full: skip the device calibration and the spread rounds behind the timed region, so that "
+                         "a rocprofv3 --stats run sees the contract's launches only (its per-kernel average is then the line's)")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="skip the PCIe-inclusive side measurement (its single-frame and host-memory launches would "
-                         "mix into the per-kernel averages of a rocprofv3 --stats run)")
+                    help="with --full: skip the PCIe-inclusive side measurement (its single-frame and host-memory launches "
+                         "would mix into the per-kernel averages of a rocprofv3 --stats run)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default=None,
                     help="torch.distributed backend for N > 1 (default: nccl = RCCL)")
     ap.add_argument("--share-gpu", action="store_true",
@@ -596,6 +632,8 @@ def main():
     a = ap.parse_args()
     if a.share_gpu and a.backend != "gloo":
         raise SystemExit("--share-gpu needs --backend gloo")
+    if not a.full:   # a plain run: the headline only
+        a.no_variants = a.no_cpu = a.no_extras = a.no_host_path = True
 
     # everything that can be refused is refused BEFORE a process group exists (a rank that dies inside
     # init_process_group leaves its peers waiting for the launcher to reap them)
@@ -648,6 +686,8 @@ def main():
     # show the sustained time of the same launch; frac and frac_sustained should agree within ~2 %.
     wall, kernel_ms, kernel_ms_first, warm_n, warm_ms = timed_steps(batch, a.steps, a.warmup, multi_gpu.barrier,
                                                                     heat_ms=a.heat_ms)
+    if a.dump_outputs:   # now: the calibration below overwrites the output buffer
+        dump_outputs(batch, a.dump_outputs, f"_rank{rank}" if world > 1 else "")
     # every rank calibrates its device on its own output buffer (plain fill / copy, >= 100 ms each)
     cal = device_calibration(ctx, batch) if not a.no_extras else None
     headline_clock = shader_clock_GHz(ctx, batch, dev) if (not a.no_extras and world == 1) else (None, [], None)

@@ -71,13 +71,13 @@ def test_workload_string_fits_the_record_and_names_the_warm_up():
 
 @pytest.mark.gpu
 def test_the_emitted_line_survives_the_driver_rule():
-    """bench.py as the driver runs it (fewer steps): the line it prints, passed through the driver's rule, still carries the
+    """bench.py --full (fewer steps): the line it prints, passed through the driver's rule, still carries the
     COMPACT and callback-body scalars, a workload string that names the time-floored warm-up, and a live shader clock."""
     import bench
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "2", "--no-cpu", "--no-host-path"],
-                       env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "8", "--warmup", "2", "--no-cpu",
+                        "--no-host-path"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -90,3 +90,58 @@ def test_the_emitted_line_survives_the_driver_rule():
     assert 0.5 < r["callback_parity_clock_GHz"] < 3.0
     assert "time-floored warm-up" in view["config"]["workload"] and len(view["config"]["workload"]) <= 120
     assert r["frac"] < 1.0 and r["achieved"] < r["peak"]
+
+
+def test_dump_outputs_is_a_fixed_sample_below_each_count(tmp_path, monkeypatch):
+    """--dump-outputs on a stand-in batch: float32 / float64 files within 64 MB, every sampled position below its frame's
+    count (nothing past a COMPACT frame's end), the points those positions hold, and the same files on a second dump."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+
+    class _Batch:
+        n_frames, stride = 16, 4096
+        points = torch.arange(16 * 4096 * 4, dtype=torch.float32).view(16, 4096, 4)
+        counts = torch.tensor([4000] * 8 + [0] + [1234] * 7, dtype=torch.int32)
+
+    bench.dump_outputs(_Batch(), str(tmp_path / "a"))
+    bench.dump_outputs(_Batch(), str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["counts.npy", "points_sample.npy", "points_sample_at.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        assert x.dtype in (np.float32, np.float64)
+        assert np.array_equal(x, np.load(tmp_path / "b" / n))
+    at = np.load(tmp_path / "a" / "points_sample_at.npy").astype(np.int64)
+    counts = _Batch.counts.numpy()
+    assert len(at) > 0 and (at[:, 1] < counts[at[:, 0]]).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "points_sample.npy"), _Batch.points.numpy()[at[:, 0], at[:, 1]])
+    assert np.array_equal(np.load(tmp_path / "a" / "counts.npy"), counts)
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """bench.py without --full: exactly --steps timed steps, the headline fields, none of the side measurements, and
+    --dump-outputs writes the last step's counts and sampled points (the counts sum to the line's points_per_step)."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 7 and rec["ms_per_step"] > 0 and rec["value"] > 0
+    assert rec["unit"] == "Mpixels/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert "cpu_baseline" not in rec and "variants_1gpu" not in rec and "device_fill_GBs_per_rank" not in rec["roofline"]
+    assert rec["roofline"]["device_fill_GBs"] is None and rec["roofline"]["callback_parity_ms"] is None
+    counts = np.load(tmp_path / "counts.npy")
+    assert counts.dtype == np.float64 and counts.sum() == rec["config"]["points_per_step"]
+    pts = np.load(tmp_path / "points_sample.npy")
+    assert pts.dtype == np.float32 and pts.shape[1] == 4 and len(pts) == len(np.load(tmp_path / "points_sample_at.npy"))
+    assert sum(os.path.getsize(tmp_path / n) for n in os.listdir(tmp_path)) <= 64 << 20

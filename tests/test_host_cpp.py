@@ -4,6 +4,7 @@ host (cv_bridge::toCvCopy "mono8" semantics, medianBlur 11) against the
 oracle.  GPU part: the whole DisparityCb (BASELINE.json configs[0]: 640x480
 uint16 as mono16) against the oracle pipeline, byte for byte in metadata."""
 import os
+import platform
 import subprocess
 
 import numpy as np
@@ -406,6 +407,18 @@ def test_multi_gpu_mode_with_one_rank(replay, tmp_path, mode, how):
     assert rec["pixels"] == 7 * 752 * 480 and rec["points"] == 7 * len(want)
 
 
+def _without_aslr():
+    """Command prefix that runs a program with address-space randomisation off for that process alone (setarch -R), or []
+    where the personality cannot be set.  GCC 11's ThreadSanitizer runtime only accepts a PIE binary mapped where a kernel
+    with 28 bits of mmap randomness puts it; under a kernel that randomises more widely it aborts before main ("FATAL:
+    ThreadSanitizer: unexpected memory mapping")."""
+    pre = ["setarch", platform.machine(), "-R"]
+    try:
+        return pre if subprocess.run(pre + ["true"], capture_output=True, timeout=30).returncode == 0 else []
+    except OSError:
+        return []
+
+
 def test_share_device_rehearsal_argument_handling_also_under_tsan(replay):
     """`--share-device` (N ranks on one device, collectives through the in-process loopback): its command-line rules,
     with the ordinary binary and with the ThreadSanitizer build (`make -C host tsan`), which must stay silent."""
@@ -414,15 +427,16 @@ def test_share_device_rehearsal_argument_handling_also_under_tsan(replay):
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:exitcode=66")
     import disparity_to_point_cloud_amd as d2pc
     for exe in (replay, tsan):
+        pre = _without_aslr() if exe == tsan else []
         for args, needle in ((("--gpus", "17", "--share-device"), "at most 16"),
                              (("--device", "0", "--share-device"), "one rank"),
                              (("--gpus", "2", "--devices", "0,1", "--share-device"), "ONE device"),
                              (("--share-device",), "--gpus N missing"),
                              (("--gpus", "2", "--share-device", "--depth", "0"), "1..8")):
-            p = subprocess.run([exe, *args], capture_output=True, text=True, timeout=60, env=env)
+            p = subprocess.run([*pre, exe, *args], capture_output=True, text=True, timeout=60, env=env)
             assert p.returncode == 2 and needle in p.stderr and "ThreadSanitizer" not in p.stderr, (exe, args, p.returncode, p.stderr)
         if d2pc.device_count() == 0:
-            p = subprocess.run([exe, "--gpus", "3", "--share-device"], capture_output=True, text=True, timeout=60, env=env)
+            p = subprocess.run([*pre, exe, "--gpus", "3", "--share-device"], capture_output=True, text=True, timeout=60, env=env)
             assert p.returncode == 5 and "no CPU path" in p.stderr and "ThreadSanitizer" not in p.stderr
 
 

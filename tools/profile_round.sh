@@ -10,7 +10,8 @@ P=gpurun_out/prof_r${N}
 # bench line printed inside this run is the one the stats must agree with
 rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_stats -o run -- python3 bench.py --steps 50 --warmup 5 --no-cpu --no-variants --no-extras > gpurun_out/bench_r${N}_under_rocprof.json 2> gpurun_out/bench_r${N}_under_rocprof.err
 echo "stats (headline) done"
-rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_stats_variants -o run -- python3 bench.py --steps 50 --warmup 5 --no-cpu --no-host-path > gpurun_out/bench_r${N}_under_rocprof_variants.json 2>> gpurun_out/bench_r${N}_under_rocprof.err
+OUT=${P%/*}   # the directory of the profiler output, beside it the bench lines
+rocprofv3 --kernel-trace --stats --output-format csv -d ${P}_stats_variants -o run -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu --no-host-path > $OUT/bench_r${N}_under_rocprof_variants.json 2>> $OUT/bench_r${N}_under_rocprof.err
 echo "stats (variants) done"
 for c in FETCH_SIZE WRITE_SIZE; do
   d=$( [ $c = FETCH_SIZE ] && echo fetch || echo write )

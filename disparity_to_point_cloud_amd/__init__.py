@@ -47,4 +47,8 @@ from .capi import (  # noqa: F401
     FUSE_OVERLAP,
     FUSE_BLACK_TO_WHITE,
     FUSE_GRAD_FILTER,
+    ScoreFilterDesc,
+    score_filter_desc_init,
+    SCORE_FORM_CV4,
+    SCORE_FORM_CV3,
 )

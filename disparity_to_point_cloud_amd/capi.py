@@ -30,7 +30,8 @@ ABI_SYMBOLS = [
     "d2pc_pipeline_release", "d2pc_fuse_desc_init", "d2pc_fuse_device", "d2pc_crop_to_square",
     "d2pc_rotate_cw_device", "d2pc_mono16_to_mono8_device", "d2pc_process_mono16",
     "d2pc_median_roi_device", "d2pc_host_alloc", "d2pc_host_free", "d2pc_make_q_flavour",
-    "d2pc_process_mono_device", "d2pc_set_reproject_form",
+    "d2pc_process_mono_device", "d2pc_set_reproject_form", "d2pc_score_filter_desc_init",
+    "d2pc_score_filter_device",
 ]
 # include/d2pc_ext.h: unstable, for bench.py / tools / tests only
 EXT_SYMBOLS = [
@@ -43,6 +44,7 @@ FORM_DEFAULT, FORM_CV24, FORM_CV4 = 0, 24, 4   # d2pc_reproject_form
 # d2pc_fusion_rule (source order of the reference's src/depth_map_fusion.cpp:162-235)
 (FUSE_WEIGHTED_AVERAGE, FUSE_MAX_DIST, FUSE_MAX_DIST_UNLESS_BLACK, FUSE_BETTER_SCORE, FUSE_ONLY_GOOD_1,
  FUSE_ONLY_GOOD_AVG, FUSE_OVERLAP, FUSE_BLACK_TO_WHITE, FUSE_GRAD_FILTER) = range(9)
+SCORE_FORM_CV4, SCORE_FORM_CV3 = 4, 3  # d2pc_score_form
 
 
 class Config(ctypes.Structure):
@@ -86,6 +88,17 @@ class FuseDesc(ctypes.Structure):
         ("planes", ctypes.c_void_p * 6), ("pitch", ctypes.c_size_t * 6), ("frame_stride", ctypes.c_size_t * 6),
         ("fused", ctypes.c_void_p), ("fused_pitch", ctypes.c_size_t), ("fused_frame_stride", ctypes.c_size_t),
         ("combined", ctypes.c_void_p), ("combined_pitch", ctypes.c_size_t), ("combined_frame_stride", ctypes.c_size_t),
+    ]
+
+
+class ScoreFilterDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("direction", ctypes.c_int32), ("form", ctypes.c_int32),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("n_frames", ctypes.c_int32),
+        ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("n", ctypes.c_int32),
+        ("src", ctypes.c_void_p), ("src_pitch", ctypes.c_size_t), ("src_frame_stride", ctypes.c_size_t),
+        ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_size_t), ("out_frame_stride", ctypes.c_size_t),
+        ("grad", ctypes.c_void_p), ("grad_pitch", ctypes.c_size_t), ("grad_frame_stride", ctypes.c_size_t),
     ]
 
 
@@ -239,6 +252,9 @@ def load_library(variant=None):
     L.d2pc_fuse_device.argtypes = [vp, ctypes.POINTER(FuseDesc), vp]
     L.d2pc_rotate_cw_device.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
                                         vp, ctypes.c_size_t, ctypes.c_size_t, vp]
+    L.d2pc_score_filter_desc_init.argtypes = [ctypes.POINTER(ScoreFilterDesc)]
+    L.d2pc_score_filter_desc_init.restype = None
+    L.d2pc_score_filter_device.argtypes = [vp, ctypes.POINTER(ScoreFilterDesc), vp]
     L.d2pc_crop_to_square.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 3
     L.d2pc_check_async_error.argtypes = [vp]
     L.d2pc_reserve_mono.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -566,6 +582,10 @@ class Context:
         """d2pc_fuse_device: fusion rule + combined confidence + 3x3 median + crop on device planes."""
         self._check(self._L.d2pc_fuse_device(self._h, ctypes.byref(desc), stream_ptr))
 
+    def score_filter_device(self, desc: "ScoreFilterDesc", stream_ptr=None):
+        """d2pc_score_filter_device: the G13 -> Sobel -> threshold -> G21 -> combine chain of MatchingScoreCb1/2."""
+        self._check(self._L.d2pc_score_filter_device(self._h, ctypes.byref(desc), stream_ptr))
+
     def rotate_cw_device(self, d_src_ptr, cols, rows, src_pitch, src_frame_stride, n_frames, d_dst_ptr, dst_pitch,
                          dst_frame_stride, stream_ptr=None):
         """d2pc_rotate_cw_device: dst(i, j) = src(rows-1-j, i) for 8-bit device frames."""
@@ -630,6 +650,12 @@ class Context:
 def fuse_desc_init() -> FuseDesc:
     d = FuseDesc()
     load_library().d2pc_fuse_desc_init(ctypes.byref(d))
+    return d
+
+
+def score_filter_desc_init() -> ScoreFilterDesc:
+    d = ScoreFilterDesc()
+    load_library().d2pc_score_filter_desc_init(ctypes.byref(d))
     return d
 
 

@@ -1,5 +1,6 @@
 // d2pc_capi_fusion.hip -- SURVEY.md section 8(f) #4: the per-pixel loop of publishFusedDepthMap
-// (reference src/depth_map_fusion.cpp:113-130), rotateMat and cropToSquare's arithmetic.
+// (reference src/depth_map_fusion.cpp:113-130), rotateMat, cropToSquare's arithmetic and the matching-score
+// pre-filter of MatchingScoreCb1/2 (:64-99).
 #include "d2pc_ctx.hpp"
 
 using namespace d2pc;
@@ -144,6 +145,77 @@ int d2pc_rotate_cw_device(d2pc_ctx *ctx, const void *d_src, int cols, int rows, 
   a.rows = uint32_t(rows);
   a.n_frames = uint32_t(n_frames);
   D2PC_HIP(ctx, launch_rotate_cw(a, static_cast<hipStream_t>(stream)));
+  return D2PC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Matching-score pre-filter (src/depth_map_fusion.cpp:64-99)
+// ---------------------------------------------------------------------------
+void d2pc_score_filter_desc_init(d2pc_score_filter_desc *desc) {
+  if (!desc) return;
+  memset(desc, 0, sizeof *desc);
+  desc->struct_size = sizeof *desc;
+  desc->direction = 0;
+  desc->form = D2PC_SCORE_FORM_CV4;
+  desc->n_frames = 1;
+}
+
+int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, void *stream) {
+  if (!ctx) return D2PC_ERR_INVALID_ARG;
+  if (!desc || desc->struct_size != sizeof(d2pc_score_filter_desc))
+    return fail(ctx, D2PC_ERR_INVALID_ARG, "bad d2pc_score_filter_desc");
+  const d2pc_score_filter_desc &d = *desc;
+  if (d.direction != 0 && d.direction != 1) return fail(ctx, D2PC_ERR_INVALID_ARG, "direction %d is not 0 or 1", d.direction);
+  if (d.form != D2PC_SCORE_FORM_CV4 && d.form != D2PC_SCORE_FORM_CV3)
+    return fail(ctx, D2PC_ERR_INVALID_ARG, "unknown score form %d", d.form);
+  if (d.width <= 0 || d.height <= 0 || d.n_frames <= 0 || d.n_frames > 65535)
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "bad size %dx%d x%d", d.width, d.height, d.n_frames);
+  // the G21 halo (10 pixels) reflects once about the square's edges: n >= 11
+  if (d.n < 11 || d.x < 0 || d.y < 0 || d.x > d.width - d.n || d.y > d.height - d.n)
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "square %d,%d,%d: n < 11 or outside %dx%d", d.x, d.y, d.n, d.width, d.height);
+  if (!d.src || !d.out) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
+  // byte extent of a (w x h) x n_frames plane; 32-bit row offsets in the kernel
+  auto extent = [&](size_t pitch, size_t fstride, int w, int h) {
+    return size_t(d.n_frames - 1) * fstride + size_t(h - 1) * pitch + size_t(w);
+  };
+  auto bad_plane = [&](size_t pitch, size_t fstride, int w, int h) {
+    return pitch < size_t(w) || pitch * size_t(h) > 0xffffffffull ||
+           (d.n_frames > 1 && fstride < size_t(h - 1) * pitch + size_t(w));
+  };
+  if (bad_plane(d.src_pitch, d.src_frame_stride, d.width, d.height))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "source pitch / frame stride too small (or plane >= 4 GiB)");
+  if (bad_plane(d.out_pitch, d.out_frame_stride, d.n, d.n))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "out pitch / frame stride too small (or plane >= 4 GiB)");
+  if (d.grad && bad_plane(d.grad_pitch, d.grad_frame_stride, d.n, d.n))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "grad pitch / frame stride too small (or plane >= 4 GiB)");
+  struct Range { uintptr_t lo, hi; };
+  auto overlaps = [](Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; };
+  auto range = [&](const void *p, size_t pitch, size_t fstride, int w, int h) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return Range{lo, lo + (p ? extent(pitch, fstride, w, h) : 0)};
+  };
+  const Range rs = range(d.src, d.src_pitch, d.src_frame_stride, d.width, d.height);
+  const Range ro = range(d.out, d.out_pitch, d.out_frame_stride, d.n, d.n);
+  const Range rg = range(d.grad, d.grad_pitch, d.grad_frame_stride, d.n, d.n);
+  if (overlaps(rs, ro) || (d.grad && overlaps(rs, rg)))
+    return fail(ctx, D2PC_ERR_INVALID_ARG, "an output overlaps the source (in-place filtering is not supported)");
+  if (d.grad && overlaps(ro, rg)) return fail(ctx, D2PC_ERR_INVALID_ARG, "out and grad overlap");
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  ScoreArgs a;
+  a.src = static_cast<const uint8_t *>(d.src);
+  a.out = static_cast<uint8_t *>(d.out);
+  a.grad = static_cast<uint8_t *>(d.grad);
+  a.src_pitch = uint32_t(d.src_pitch);
+  a.out_pitch = uint32_t(d.out_pitch);
+  a.grad_pitch = uint32_t(d.grad_pitch);
+  a.src_frame_stride = d.n_frames > 1 ? d.src_frame_stride : 0;
+  a.out_frame_stride = d.n_frames > 1 ? d.out_frame_stride : 0;
+  a.grad_frame_stride = d.n_frames > 1 ? d.grad_frame_stride : 0;
+  a.width = d.width, a.height = d.height, a.x0 = d.x, a.y0 = d.y, a.n = d.n, a.n_frames = d.n_frames;
+  a.direction = d.direction;
+  a.form = d.form;
+  D2PC_HIP(ctx, launch_score_filter(a, static_cast<hipStream_t>(stream)));
   return D2PC_OK;
 }
 

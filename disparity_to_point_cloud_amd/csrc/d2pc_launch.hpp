@@ -98,6 +98,20 @@ struct RotateArgs {
 };
 hipError_t launch_rotate_cw(RotateArgs a, hipStream_t stream);
 
+// Matching-score pre-filter of MatchingScoreCb1/2 (d2pc_score.hip): G13 on the frame -> Sobel -> threshold -> G21
+// -> score + 2 * G21 on the n x n square at (x0, y0).  Tap tables are launch data.
+struct ScoreArgs {
+  const uint8_t *src = nullptr;
+  uint8_t *out = nullptr, *grad = nullptr;  // grad nullable
+  uint64_t src_frame_stride = 0, out_frame_stride = 0, grad_frame_stride = 0;
+  uint32_t src_pitch = 0, out_pitch = 0, grad_pitch = 0;
+  int32_t width = 0, height = 0, x0 = 0, y0 = 0, n = 0, n_frames = 1;
+  int32_t direction = 0, form = 4;
+  int32_t t13[13] = {}, t21[21] = {};
+  int32_t tiles = 0;  // filled by launch_score_filter
+};
+hipError_t launch_score_filter(ScoreArgs a, hipStream_t stream);
+
 bool tile_shape_supported(int pxt);
 uint32_t frame_state_stride(uint32_t tiles_per_frame);
 size_t compact_state_bytes(const Geom &g);

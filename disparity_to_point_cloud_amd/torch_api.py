@@ -89,3 +89,34 @@ def fuse_planes(ctx: capi.Context, planes, rule=capi.FUSE_GRAD_FILTER, crop=(0, 
         fused = fused[0]
         combined = combined[0] if want_combined else None
     return fused, combined
+
+
+def score_filter(ctx: capi.Context, frames, square, direction, form=capi.SCORE_FORM_CV4, want_grad=False, stream=None):
+    """d2pc_score_filter_device on a torch uint8 CUDA tensor: the matching-score pre-filter of MatchingScoreCb1/2.
+
+    frames: (H, W) or (F, H, W) with unit column stride (row/frame strides are free, so views work); camera 2's
+    frames already rotated.  square = (x, y, n) from crop_to_square; direction 0 = Sobel(0,2) (camera 1), 1 =
+    Sobel(2,0) (camera 2); form = SCORE_FORM_CV4 / SCORE_FORM_CV3.  Returns (out, grad or None) as new (F,) n x n
+    tensors; asynchronous on `stream` (default: torch's current stream)."""
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (2, 3) and frames.stride(-1) == 1
+    batched = frames.dim() == 3
+    f, h, w = tuple(frames.shape) if batched else (1,) + tuple(frames.shape)
+    x, y, n = square
+    desc = capi.score_filter_desc_init()
+    desc.direction, desc.form = direction, form
+    desc.width, desc.height, desc.n_frames = w, h, f
+    desc.x, desc.y, desc.n = x, y, n
+    desc.src, desc.src_pitch = frames.data_ptr(), frames.stride(-2)
+    desc.src_frame_stride = frames.stride(0) if batched else 0
+    out = torch.empty((f, n, n), dtype=torch.uint8, device=frames.device)
+    desc.out, desc.out_pitch, desc.out_frame_stride = out.data_ptr(), n, n * n
+    grad = None
+    if want_grad:
+        grad = torch.empty((f, n, n), dtype=torch.uint8, device=frames.device)
+        desc.grad, desc.grad_pitch, desc.grad_frame_stride = grad.data_ptr(), n, n * n
+    s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+    ctx.score_filter_device(desc, s.cuda_stream)
+    if not batched:
+        out = out[0]
+        grad = grad[0] if want_grad else None
+    return out, grad

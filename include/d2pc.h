@@ -474,6 +474,43 @@ int d2pc_rotate_cw_device(d2pc_ctx *ctx, const void *d_src, int cols, int rows, 
 int d2pc_crop_to_square(int cols, int rows, int offset_x, int offset_y, int member_offset_y,
                         int *x, int *y, int *n);
 
+/*
+ * The matching-score pre-filter of MatchingScoreCb1/2 (src/depth_map_fusion.cpp:64-99) on the device:
+ *   A   = GaussianBlur(square, 13x13, 3)                 (:70,:89)  the square is a VIEW (cropToSquare, :66,:85):
+ *                                                                   the blur reads the frame's pixels round it and
+ *                                                                   reflects (reflect101) only about the FRAME's edges
+ *   M   = threshold(Sobel(A, -1, dx, dy, 7, 0.03), 30)   (:72-73,:91-92)  direction 0: (0,2), 1: (2,0);
+ *                                                                   reflect101 about the square's edges
+ *   B   = GaussianBlur(M, 21x21, 10)                     (:74,:93)  reflect101 about the square's edges
+ *   out = square + 2 * B, saturated                      (:76,:95)  what the reference keeps as both the score
+ *                                                                   and the grad plane (:77,:96)
+ * in exact integers.  The two forms differ only in B: D2PC_SCORE_FORM_CV4 takes OpenCV 4.x's
+ * bit-exact fixed-point Gaussian (taps sum 256, rounds half up), D2PC_SCORE_FORM_CV3 OpenCV 3.2's general 8-bit
+ * path (taps sum 254, rounds half to even).  A is the same in both (general path: a view is never bit-exact).
+ */
+typedef enum d2pc_score_form { D2PC_SCORE_FORM_CV4 = 4, D2PC_SCORE_FORM_CV3 = 3 } d2pc_score_form;
+
+typedef struct d2pc_score_filter_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_score_filter_desc) */
+  int32_t direction;           /* 0: Sobel(0,2) of MatchingScoreCb1, 1: Sobel(2,0) of MatchingScoreCb2 */
+  int32_t form;                /* d2pc_score_form */
+  int32_t width, height;       /* of the source frames (camera 2: already rotated, d2pc_rotate_cw_device) */
+  int32_t n_frames;            /* independent frames, frame strides apart */
+  int32_t x, y, n;             /* the square (d2pc_crop_to_square); n >= 11 */
+  const void *src;             /* DEVICE: 8-bit frames */
+  size_t src_pitch, src_frame_stride;
+  void *out;                   /* DEVICE out: n x n, min(255, score + 2 B) */
+  size_t out_pitch, out_frame_stride;
+  void *grad;                  /* DEVICE out, nullable: n x n, B (before the combine) */
+  size_t grad_pitch, grad_frame_stride;
+} d2pc_score_filter_desc;
+
+/* struct_size, direction 0, D2PC_SCORE_FORM_CV4, n_frames 1; everything else zero. */
+void d2pc_score_filter_desc_init(d2pc_score_filter_desc *desc);
+/* Asynchronous on `stream` (NULL = the HIP default stream).  Outputs must not overlap the source or each other
+ * (no in-place filtering). */
+int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,4 +51,15 @@ from .capi import (  # noqa: F401
     score_filter_desc_init,
     SCORE_FORM_CV4,
     SCORE_FORM_CV3,
+    ColorizeDesc,
+    colorize_desc_init,
+    colorize_table,
 )
+
+
+def __getattr__(name):
+    # the fusion-node session needs torch; the binding above does not, so torch is imported on first use only
+    if name == "FusionNode":
+        from .fusion_node import FusionNode
+        return FusionNode
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "d2pc_rotate_cw_device", "d2pc_mono16_to_mono8_device", "d2pc_process_mono16",
     "d2pc_median_roi_device", "d2pc_host_alloc", "d2pc_host_free", "d2pc_make_q_flavour",
     "d2pc_process_mono_device", "d2pc_set_reproject_form", "d2pc_score_filter_desc_init",
-    "d2pc_score_filter_device",
+    "d2pc_score_filter_device", "d2pc_colorize_table", "d2pc_colorize_desc_init", "d2pc_colorize_device",
 ]
 # include/d2pc_ext.h: unstable, for bench.py / tools / tests only
 EXT_SYMBOLS = [
@@ -99,6 +99,17 @@ class ScoreFilterDesc(ctypes.Structure):
         ("src", ctypes.c_void_p), ("src_pitch", ctypes.c_size_t), ("src_frame_stride", ctypes.c_size_t),
         ("out", ctypes.c_void_p), ("out_pitch", ctypes.c_size_t), ("out_frame_stride", ctypes.c_size_t),
         ("grad", ctypes.c_void_p), ("grad_pitch", ctypes.c_size_t), ("grad_frame_stride", ctypes.c_size_t),
+    ]
+
+
+class ColorizeDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("rotate_cw", ctypes.c_int32), ("cols", ctypes.c_int32),
+        ("rows", ctypes.c_int32), ("n_frames", ctypes.c_int32),
+        ("x", ctypes.c_int32), ("y", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+        ("src", ctypes.c_void_p), ("src_pitch", ctypes.c_size_t), ("src_frame_stride", ctypes.c_size_t),
+        ("gray", ctypes.c_void_p), ("gray_pitch", ctypes.c_size_t), ("gray_frame_stride", ctypes.c_size_t),
+        ("rgb", ctypes.c_void_p), ("rgb_pitch", ctypes.c_size_t), ("rgb_frame_stride", ctypes.c_size_t),
     ]
 
 
@@ -255,6 +266,10 @@ def load_library(variant=None):
     L.d2pc_score_filter_desc_init.argtypes = [ctypes.POINTER(ScoreFilterDesc)]
     L.d2pc_score_filter_desc_init.restype = None
     L.d2pc_score_filter_device.argtypes = [vp, ctypes.POINTER(ScoreFilterDesc), vp]
+    L.d2pc_colorize_table.argtypes = [ctypes.POINTER(ctypes.c_uint8)]
+    L.d2pc_colorize_desc_init.argtypes = [ctypes.POINTER(ColorizeDesc)]
+    L.d2pc_colorize_desc_init.restype = None
+    L.d2pc_colorize_device.argtypes = [vp, ctypes.POINTER(ColorizeDesc), vp]
     L.d2pc_crop_to_square.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 3
     L.d2pc_check_async_error.argtypes = [vp]
     L.d2pc_reserve_mono.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -586,6 +601,10 @@ class Context:
         """d2pc_score_filter_device: the G13 -> Sobel -> threshold -> G21 -> combine chain of MatchingScoreCb1/2."""
         self._check(self._L.d2pc_score_filter_device(self._h, ctypes.byref(desc), stream_ptr))
 
+    def colorize_device(self, desc: "ColorizeDesc", stream_ptr=None):
+        """d2pc_colorize_device: the view of DisparityCb1/2 (optionally of the rotated frame) and its colorizeDepth."""
+        self._check(self._L.d2pc_colorize_device(self._h, ctypes.byref(desc), stream_ptr))
+
     def rotate_cw_device(self, d_src_ptr, cols, rows, src_pitch, src_frame_stride, n_frames, d_dst_ptr, dst_pitch,
                          dst_frame_stride, stream_ptr=None):
         """d2pc_rotate_cw_device: dst(i, j) = src(rows-1-j, i) for 8-bit device frames."""
@@ -657,6 +676,22 @@ def score_filter_desc_init() -> ScoreFilterDesc:
     d = ScoreFilterDesc()
     load_library().d2pc_score_filter_desc_init(ctypes.byref(d))
     return d
+
+
+def colorize_desc_init() -> ColorizeDesc:
+    d = ColorizeDesc()
+    load_library().d2pc_colorize_desc_init(ctypes.byref(d))
+    return d
+
+
+def colorize_table() -> np.ndarray:
+    """d2pc_colorize_table -> (256, 3) uint8: row g is the three bytes colorizeDepth writes for pixel g, in memory
+    order.  Host only."""
+    t = np.zeros((256, 3), dtype=np.uint8)
+    st = load_library().d2pc_colorize_table(t.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if st != 0:
+        raise D2pcError(st, "colorize_table")
+    return t
 
 
 def crop_to_square(cols, rows, offset_x=0, offset_y=0, member_offset_y=None):

@@ -1,6 +1,6 @@
 // d2pc_capi_fusion.hip -- SURVEY.md section 8(f) #4: the per-pixel loop of publishFusedDepthMap
-// (reference src/depth_map_fusion.cpp:113-130), rotateMat, cropToSquare's arithmetic and the matching-score
-// pre-filter of MatchingScoreCb1/2 (:64-99).
+// (reference src/depth_map_fusion.cpp:113-130), rotateMat, cropToSquare's arithmetic, the matching-score
+// pre-filter of MatchingScoreCb1/2 (:64-99) and colorizeDepth with the view of DisparityCb1/2 (:45-61, :306-360).
 #include "d2pc_ctx.hpp"
 
 using namespace d2pc;
@@ -216,6 +216,78 @@ int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, 
   a.direction = d.direction;
   a.form = d.form;
   D2PC_HIP(ctx, launch_score_filter(a, static_cast<hipStream_t>(stream)));
+  return D2PC_OK;
+}
+
+
+// ---------------------------------------------------------------------------
+// colorizeDepth + the view of DisparityCb1/2 (src/depth_map_fusion.cpp:45-61,306-360)
+// ---------------------------------------------------------------------------
+int d2pc_colorize_table(uint8_t table[768]) {
+  if (!table) return D2PC_ERR_INVALID_ARG;
+  colorize_table(table);
+  return D2PC_OK;
+}
+
+void d2pc_colorize_desc_init(d2pc_colorize_desc *desc) {
+  if (!desc) return;
+  memset(desc, 0, sizeof *desc);
+  desc->struct_size = sizeof *desc;
+  desc->rotate_cw = 0;
+  desc->n_frames = 1;
+}
+
+int d2pc_colorize_device(d2pc_ctx *ctx, const d2pc_colorize_desc *desc, void *stream) {
+  if (!ctx) return D2PC_ERR_INVALID_ARG;
+  if (!desc || desc->struct_size != sizeof(d2pc_colorize_desc)) return fail(ctx, D2PC_ERR_INVALID_ARG, "bad d2pc_colorize_desc");
+  const d2pc_colorize_desc &d = *desc;
+  if (d.rotate_cw != 0 && d.rotate_cw != 1) return fail(ctx, D2PC_ERR_INVALID_ARG, "rotate_cw %d is not 0 or 1", d.rotate_cw);
+  if (d.cols <= 0 || d.rows <= 0 || d.n_frames <= 0 || d.n_frames > 65535)
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "bad size %dx%d x%d", d.cols, d.rows, d.n_frames);
+  // the frame the view is taken of: rotated, it has `cols` rows of `rows` pixels
+  const int fw = d.rotate_cw ? d.rows : d.cols, fh = d.rotate_cw ? d.cols : d.rows;
+  if (d.w <= 0 || d.h <= 0 || d.x < 0 || d.y < 0 || d.x > fw - d.w || d.y > fh - d.h)
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "view %d,%d %dx%d: empty or outside %dx%d", d.x, d.y, d.w, d.h, fw, fh);
+  if (!d.src) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
+  if (!d.gray && !d.rgb) return fail(ctx, D2PC_ERR_INVALID_ARG, "neither gray nor rgb output");
+  // a plane of n_frames x (h rows of `row` bytes)
+  auto extent = [&](size_t pitch, size_t fstride, size_t row, int h) {
+    return size_t(d.n_frames - 1) * fstride + size_t(h - 1) * pitch + row;
+  };
+  auto bad_plane = [&](size_t pitch, size_t fstride, size_t row, int h) {
+    return pitch < row || pitch > 0xffffffffull || (d.n_frames > 1 && fstride < size_t(h - 1) * pitch + row);
+  };
+  if (bad_plane(d.src_pitch, d.src_frame_stride, size_t(d.cols), d.rows))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "source pitch / frame stride too small");
+  if (d.gray && bad_plane(d.gray_pitch, d.gray_frame_stride, size_t(d.w), d.h))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "gray pitch / frame stride too small");
+  if (d.rgb && bad_plane(d.rgb_pitch, d.rgb_frame_stride, 3 * size_t(d.w), d.h))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "rgb pitch (< 3 w) / frame stride too small");
+  struct Range { uintptr_t lo, hi; };
+  auto overlaps = [](Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; };
+  auto range = [&](const void *p, size_t pitch, size_t fstride, size_t row, int h) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return Range{lo, lo + (p ? extent(pitch, fstride, row, h) : 0)};
+  };
+  const Range rs = range(d.src, d.src_pitch, d.src_frame_stride, size_t(d.cols), d.rows);
+  const Range rg = range(d.gray, d.gray_pitch, d.gray_frame_stride, size_t(d.w), d.h);
+  const Range rc = range(d.rgb, d.rgb_pitch, d.rgb_frame_stride, 3 * size_t(d.w), d.h);
+  if ((d.gray && overlaps(rs, rg)) || (d.rgb && overlaps(rs, rc)))
+    return fail(ctx, D2PC_ERR_INVALID_ARG, "an output overlaps the source");
+  if (d.gray && d.rgb && overlaps(rg, rc)) return fail(ctx, D2PC_ERR_INVALID_ARG, "gray and rgb overlap");
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  ColorizeArgs a;
+  a.src = static_cast<const uint8_t *>(d.src);
+  a.gray = static_cast<uint8_t *>(d.gray);
+  a.rgb = static_cast<uint8_t *>(d.rgb);
+  a.src_pitch = d.src_pitch, a.gray_pitch = d.gray_pitch, a.rgb_pitch = d.rgb_pitch;
+  a.src_frame_stride = d.n_frames > 1 ? d.src_frame_stride : 0;
+  a.gray_frame_stride = d.n_frames > 1 ? d.gray_frame_stride : 0;
+  a.rgb_frame_stride = d.n_frames > 1 ? d.rgb_frame_stride : 0;
+  a.cols = d.cols, a.rows = d.rows, a.x = d.x, a.y = d.y, a.w = d.w, a.h = d.h;
+  a.n_frames = d.n_frames, a.rotate_cw = d.rotate_cw;
+  D2PC_HIP(ctx, launch_colorize(a, static_cast<hipStream_t>(stream)));
   return D2PC_OK;
 }
 

@@ -112,6 +112,23 @@ struct ScoreArgs {
 };
 hipError_t launch_score_filter(ScoreArgs a, hipStream_t stream);
 
+// colorizeDepth of a view of 8-bit frames, optionally of the frames rotated 90 degrees clockwise (d2pc_colorize.hip;
+// DESIGN.md section 8b).  The 256-entry colour table is launch data: entry g = byte0 | byte1 << 8 | byte2 << 16.
+struct ColorizeArgs {
+  const uint8_t *src = nullptr;
+  uint8_t *gray = nullptr, *rgb = nullptr;  // either nullable, not both
+  uint64_t src_frame_stride = 0, gray_frame_stride = 0, rgb_frame_stride = 0;
+  uint64_t src_pitch = 0, gray_pitch = 0, rgb_pitch = 0;
+  int32_t cols = 0, rows = 0;              // source frame as stored
+  int32_t x = 0, y = 0, w = 0, h = 0;      // view in the (rotated) frame
+  int32_t n_frames = 1, rotate_cw = 0;
+  uint32_t tiles_x = 0, tiles_y = 0;       // filled by launch_colorize
+  uint32_t table[256] = {};                // filled by launch_colorize
+};
+hipError_t launch_colorize(ColorizeArgs a, hipStream_t stream);
+// The table itself (host): row g is bytes 3g .. 3g + 2.
+void colorize_table(uint8_t table[768]);
+
 bool tile_shape_supported(int pxt);
 uint32_t frame_state_stride(uint32_t tiles_per_frame);
 size_t compact_state_bytes(const Geom &g);

@@ -120,3 +120,41 @@ def score_filter(ctx: capi.Context, frames, square, direction, form=capi.SCORE_F
         out = out[0]
         grad = grad[0] if want_grad else None
     return out, grad
+
+
+def colorize(ctx: capi.Context, frames, view=None, rotate_cw=False, want_gray=False, stream=None):
+    """d2pc_colorize_device on a torch uint8 CUDA tensor: the view cropToSquare takes in DisparityCb1/2 and its
+    colorizeDepth, in one launch.
+
+    frames: (H, W) or (F, H, W) with unit column stride (row/frame strides are free, so views work).  rotate_cw: take
+    the view of the frames rotated 90 degrees clockwise (camera 2) without materialising them.  view = (x, y, w, h)
+    in the (rotated) frame's coordinates, or (x, y, n) from crop_to_square, or None for the whole plane.  Returns
+    (rgb (F,) h x w x 3, gray (F,) h x w or None) as new tensors; asynchronous on `stream` (default: torch's current
+    stream)."""
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (2, 3) and frames.stride(-1) == 1
+    batched = frames.dim() == 3
+    f, rows, cols = tuple(frames.shape) if batched else (1,) + tuple(frames.shape)
+    fw, fh = (rows, cols) if rotate_cw else (cols, rows)
+    if view is None:
+        view = (0, 0, fw, fh)
+    elif len(view) == 3:
+        view = (view[0], view[1], view[2], view[2])
+    x, y, w, h = view
+    desc = capi.colorize_desc_init()
+    desc.rotate_cw, desc.cols, desc.rows, desc.n_frames = int(bool(rotate_cw)), cols, rows, f
+    desc.x, desc.y, desc.w, desc.h = x, y, w, h
+    desc.src, desc.src_pitch = frames.data_ptr(), frames.stride(-2)
+    desc.src_frame_stride = frames.stride(0) if batched else 0
+    shape = (f, max(h, 0), max(w, 0))
+    rgb = torch.empty(shape + (3,), dtype=torch.uint8, device=frames.device)
+    desc.rgb, desc.rgb_pitch, desc.rgb_frame_stride = rgb.data_ptr(), 3 * w, 3 * w * h
+    gray = None
+    if want_gray:
+        gray = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+        desc.gray, desc.gray_pitch, desc.gray_frame_stride = gray.data_ptr(), w, w * h
+    s = stream if stream is not None else torch.cuda.current_stream(frames.device)
+    ctx.colorize_device(desc, s.cuda_stream)
+    if not batched:
+        rgb = rgb[0]
+        gray = gray[0] if want_gray else None
+    return rgb, gray

@@ -460,7 +460,8 @@ typedef struct d2pc_fuse_desc {
 void d2pc_fuse_desc_init(d2pc_fuse_desc *desc);
 /* Asynchronous on `stream` (NULL = the HIP default stream).  Outputs must not
  * overlap the inputs or each other: the reference writes `combined` over
- * score1 in place (cpp:113), which a caller reproduces by swapping buffers. */
+ * score1 in place (cpp:113), which a caller reproduces by swapping buffers
+ * (the Python FusionNode session does). */
 int d2pc_fuse_device(d2pc_ctx *ctx, const d2pc_fuse_desc *desc, void *stream);
 /* rotateMat (src/depth_map_fusion.cpp:268-273: cv::transpose + cv::flip(.,1) = 90 degrees clockwise) of 8-bit
  * frames on the device: dst has `cols` rows of `rows` pixels, dst(i,j) = src(rows-1-j, i).  What DisparityCb2 and
@@ -510,6 +511,43 @@ void d2pc_score_filter_desc_init(d2pc_score_filter_desc *desc);
 /* Asynchronous on `stream` (NULL = the HIP default stream).  Outputs must not overlap the source or each other
  * (no in-place filtering). */
 int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, void *stream);
+
+/*
+ * colorizeDepth (src/depth_map_fusion.cpp:306-360): the RAINBOW_WITH_BLACK colouring of the /cropped_depth_1,
+ * /cropped_depth_2 and /gradient topics.  A function of the 8-bit pixel alone, so a 256 x 3 table (DESIGN.md
+ * section 8b): row g is bytes 3g .. 3g+2 in MEMORY order (the reference names them b, g, r and publishes the buffer
+ * as "rgb8").  Computed on the host in IEEE float32, one rounding per operation; rows 0 and 1 are black.
+ * Host only: no context, no GPU.  Returns D2PC_OK, or D2PC_ERR_INVALID_ARG for NULL.
+ */
+int d2pc_colorize_table(uint8_t table[768]);
+
+/*
+ * The body of DisparityCb1 / DisparityCb2 (:45-61) and of the /gradient publish (:132) in one launch: take a w x h
+ * view of each 8-bit frame -- optionally of the frame rotated 90 degrees clockwise, as d2pc_rotate_cw_device
+ * defines it (dst(i,j) = src(rows-1-j, i)), WITHOUT materialising the rotated frame -- and write the view itself
+ * (`gray`, the reference's cropped_depth_k_) and / or its colouring (`rgb`, w x h x 3 bytes).  Neither output needs
+ * any alignment: a packed rgb image has pitch 3w, odd for odd w.
+ */
+typedef struct d2pc_colorize_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_colorize_desc) */
+  int32_t rotate_cw;           /* 0: view of the frame; 1: view of the frame rotated 90 degrees clockwise */
+  int32_t cols, rows;          /* of the source frames as stored (before the rotation) */
+  int32_t n_frames;            /* independent frames, frame strides apart */
+  int32_t x, y, w, h;          /* the view, in the (rotated) frame's coordinates: what d2pc_crop_to_square returns,
+                                  or 0, 0 and the whole (rotated) plane */
+  const void *src;             /* DEVICE: 8-bit frames */
+  size_t src_pitch, src_frame_stride;
+  void *gray;                  /* DEVICE out, nullable: w x h, the view copied */
+  size_t gray_pitch, gray_frame_stride;
+  void *rgb;                   /* DEVICE out, nullable: w x h x 3 bytes, pitch >= 3 w */
+  size_t rgb_pitch, rgb_frame_stride;
+} d2pc_colorize_desc;
+
+/* struct_size, rotate_cw 0, n_frames 1; everything else zero. */
+void d2pc_colorize_desc_init(d2pc_colorize_desc *desc);
+/* Asynchronous on `stream` (NULL = the HIP default stream); no scratch memory, so it can be captured into a graph
+ * as it is.  At least one output; outputs must not overlap the source or each other. */
+int d2pc_colorize_device(d2pc_ctx *ctx, const d2pc_colorize_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

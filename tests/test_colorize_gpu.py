@@ -1,0 +1,268 @@
+"""d2pc_colorize_device on the GPU, bit for bit against the restatement tests/colorize_ref.py:
+every byte value, both outputs, rotated and not, odd and tiny sizes, unaligned pitches and base addresses with guard
+bytes, views at every frame edge, batches, strided sources, misuse, graph capture and a sampled 4K batch."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import disparity_to_point_cloud_amd as d2pc
+import oracle
+import colorize_ref as ref
+from disparity_to_point_cloud_amd.torch_api import colorize
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with d2pc.Context(q=d2pc.make_q()) as c:
+        yield c
+
+
+def _want(frame, view, rotate):
+    return ref.colorize_view(frame, view, rotate)
+
+
+def _check(ctx, frame, view=None, rotate=False, want_gray=True):
+    rgb, gray = colorize(ctx, torch.from_numpy(frame).cuda(), view, rotate, want_gray=want_gray)
+    torch.cuda.synchronize()
+    wr, wg = _want(frame, view, rotate)
+    assert np.array_equal(rgb.cpu().numpy(), wr), (frame.shape, view, rotate)
+    if want_gray:
+        assert np.array_equal(gray.cpu().numpy(), wg), (frame.shape, view, rotate)
+    else:
+        assert gray is None
+
+
+@pytest.mark.parametrize("rotate", [False, True])
+def test_all_byte_values(ctx, rotate):
+    img = np.arange(256, dtype=np.uint8).reshape(16, 16)
+    _check(ctx, img, None, rotate)
+    _check(ctx, img, None, rotate, want_gray=False)
+    wide = np.tile(np.arange(256, dtype=np.uint8), (3, 2))[:, 5:5 + 300].copy()
+    _check(ctx, wide, None, rotate)
+    rgb, _ = colorize(ctx, torch.from_numpy(img).cuda(), None, rotate)
+    t = d2pc.colorize_table()
+    src = oracle.rotate_cw(img) if rotate else img
+    assert np.array_equal(rgb.cpu().numpy(), t[src])  # ... and against the library's own host table
+
+
+@pytest.mark.parametrize("h,w", [(1, 1), (1, 7), (7, 1), (3, 5), (5, 3), (465, 465), (425, 425), (64, 128), (65, 129),
+                                 (63, 127), (130, 300), (300, 130)])
+def test_odd_tiny_landscape_portrait(ctx, h, w):
+    rng = np.random.default_rng(1000 * h + w)
+    img = rng.integers(0, 256, size=(h, w)).astype(np.uint8)
+    for rotate in (False, True):
+        _check(ctx, img, None, rotate)
+        _check(ctx, img, None, rotate, want_gray=False)
+
+
+def test_views_at_every_frame_edge(ctx):
+    rng = np.random.default_rng(2)
+    h, w = 150, 170
+    img = rng.integers(0, 256, size=(h, w)).astype(np.uint8)
+    for rotate in (False, True):
+        fw, fh = (h, w) if rotate else (w, h)
+        for vw, vh in ((1, 1), (5, 9), (127, 63), (129, 65), (fw, fh), (fw - 1, fh - 1), (131, 140)):
+            for x in sorted({0, 1, (fw - vw) // 2, fw - vw - 1, fw - vw}):
+                for y in sorted({0, 1, (fh - vh) // 2, fh - vh}):
+                    if 0 <= x <= fw - vw and 0 <= y <= fh - vh:
+                        _check(ctx, img, (x, y, vw, vh), rotate)
+
+
+def test_rotate_and_view_is_rotate_then_slice(ctx):
+    rng = np.random.default_rng(3)
+    H, W = 480, 752
+    img = rng.integers(0, 256, size=(H, W)).astype(np.uint8)
+    x, y, n = d2pc.crop_to_square(H, W, 7, -15, 15)
+    assert n == 465
+    rgb, gray = colorize(ctx, torch.from_numpy(img).cuda(), (x, y, n), rotate_cw=True, want_gray=True)
+    torch.cuda.synchronize()
+    want = oracle.rotate_cw(img)[y:y + n, x:x + n]
+    assert np.array_equal(gray.cpu().numpy(), want)
+    assert np.array_equal(rgb.cpu().numpy(), ref.table()[want])
+    x, y, n = d2pc.crop_to_square(W, H, -7, 15)
+    rgb, gray = colorize(ctx, torch.from_numpy(img).cuda(), (x, y, n), want_gray=True)
+    assert np.array_equal(gray.cpu().numpy(), img[y:y + n, x:x + n])
+    assert np.array_equal(rgb.cpu().numpy(), ref.table()[img[y:y + n, x:x + n]])
+
+
+def _desc(src, cols, rows, view, rotate, f=1):
+    d = d2pc.colorize_desc_init()
+    d.rotate_cw, d.cols, d.rows, d.n_frames = int(rotate), cols, rows, f
+    d.x, d.y, d.w, d.h = view
+    d.src, d.src_pitch, d.src_frame_stride = src.data_ptr(), src.stride(-2), (src.stride(0) if src.dim() == 3 else 0)
+    return d
+
+
+@pytest.mark.parametrize("rotate", [False, True])
+def test_unaligned_pitches_bases_batches_and_guards(ctx, rotate):
+    """Packed 3w pitch with odd w, padded pitches, output bases offset by 0..3 bytes, frame strides that are not
+    multiples of four, a strided source view: every byte outside the outputs keeps its guard value."""
+    rng = np.random.default_rng(4 + rotate)
+    f, h, w = 3, 70, 141
+    big = torch.from_numpy(rng.integers(0, 256, size=(f + 2, h + 5, w + 11)).astype(np.uint8)).cuda()
+    src = big[1:1 + f, 2:2 + h, 3:3 + w]  # row pitch w + 11, offset origin
+    host = src.cpu().numpy()
+    fw, fh = (h, w) if rotate else (w, h)
+    stream = torch.cuda.current_stream().cuda_stream
+    for vw, vh in ((fw, fh), (37, 29), (1, 3), (65, 66)):
+        view = ((fw - vw) // 2, (fh - vh) // 3, vw, vh)
+        for off in (0, 1, 2, 3):
+            for pad in (0, 1, 2, 7):
+                gp, rp = vw + pad, 3 * vw + pad
+                gfs, rfs = gp * vh + (pad + 1), rp * vh + (pad + 3)
+                gbuf = torch.full((off + f * gfs + 8,), 7, dtype=torch.uint8, device="cuda")
+                rbuf = torch.full((off + f * rfs + 8,), 7, dtype=torch.uint8, device="cuda")
+                d = _desc(src, w, h, view, rotate, f)
+                d.gray, d.gray_pitch, d.gray_frame_stride = gbuf.data_ptr() + off, gp, gfs
+                d.rgb, d.rgb_pitch, d.rgb_frame_stride = rbuf.data_ptr() + off, rp, rfs
+                ctx.colorize_device(d, stream)
+                torch.cuda.synchronize()
+                g, r = gbuf.cpu().numpy(), rbuf.cpu().numpy()
+                wg_all, wr_all = np.full_like(g, 7), np.full_like(r, 7)
+                for k in range(f):
+                    wr, wg = _want(host[k], view[:4], rotate)
+                    for y in range(vh):
+                        o = off + k * gfs + y * gp
+                        wg_all[o:o + vw] = wg[y]
+                        o = off + k * rfs + y * rp
+                        wr_all[o:o + 3 * vw] = wr[y].reshape(-1)
+                assert np.array_equal(g, wg_all), (view, off, pad)
+                assert np.array_equal(r, wr_all), (view, off, pad)
+
+
+def test_tensor_slices_as_outputs(ctx):
+    """Output base addresses offset by 1, 2 and 3 bytes through tensor slices, rgb only and gray only."""
+    rng = np.random.default_rng(6)
+    h, w = 33, 135
+    img = rng.integers(0, 256, size=(h, w)).astype(np.uint8)
+    src = torch.from_numpy(img).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+    for off in (1, 2, 3):
+        rbuf = torch.full((h * 3 * w + 16,), 9, dtype=torch.uint8, device="cuda")
+        out = rbuf[off:off + h * 3 * w]
+        d = _desc(src, w, h, (0, 0, w, h), False)
+        d.rgb, d.rgb_pitch = out.data_ptr(), 3 * w
+        ctx.colorize_device(d, stream)
+        gbuf = torch.full((h * w + 16,), 9, dtype=torch.uint8, device="cuda")
+        gout = gbuf[off:off + h * w]
+        d = _desc(src, w, h, (0, 0, w, h), False)
+        d.gray, d.gray_pitch = gout.data_ptr(), w
+        ctx.colorize_device(d, stream)
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy().reshape(h, w, 3), ref.colorize(img))
+        assert np.array_equal(gout.cpu().numpy().reshape(h, w), img)
+        for buf, n in ((rbuf, h * 3 * w), (gbuf, h * w)):
+            b = buf.cpu().numpy()
+            assert (b[:off] == 9).all() and (b[off + n:] == 9).all()
+
+
+def test_misuse_returns_codes_without_launching(ctx):
+    h, w, vw, vh = 64, 80, 50, 40
+    src = torch.zeros((2, h, w), dtype=torch.uint8, device="cuda")
+    gray = torch.full((2, vh, vw), 99, dtype=torch.uint8, device="cuda")
+    rgb = torch.full((2, vh, vw, 3), 99, dtype=torch.uint8, device="cuda")
+    lib = d2pc.load_library()
+
+    def good():
+        d = d2pc.colorize_desc_init()
+        d.cols, d.rows, d.n_frames, d.x, d.y, d.w, d.h = w, h, 2, 10, 5, vw, vh
+        d.src, d.src_pitch, d.src_frame_stride = src.data_ptr(), w, w * h
+        d.gray, d.gray_pitch, d.gray_frame_stride = gray.data_ptr(), vw, vw * vh
+        d.rgb, d.rgb_pitch, d.rgb_frame_stride = rgb.data_ptr(), 3 * vw, 3 * vw * vh
+        return d
+
+    def both_null(d):
+        d.gray = None
+        d.rgb = None
+
+    def rotated_outside(d):  # rotated, the frame is 64 wide: x + w = 10 + 60 leaves it, though it fits unrotated
+        d.rotate_cw, d.w = 1, 60
+
+    INV, SIZE = 1, 3
+    cases = [
+        ("struct_size", lambda d: setattr(d, "struct_size", 12), INV),
+        ("rotate_cw", lambda d: setattr(d, "rotate_cw", 2), INV),
+        ("cols", lambda d: setattr(d, "cols", 0), SIZE),
+        ("frames", lambda d: setattr(d, "n_frames", 0), SIZE),
+        ("w", lambda d: setattr(d, "w", 0), SIZE),
+        ("x<0", lambda d: setattr(d, "x", -1), SIZE),
+        ("outside x", lambda d: setattr(d, "x", w - vw + 1), SIZE),
+        ("outside y", lambda d: setattr(d, "y", h - vh + 1), SIZE),
+        ("outside rotated", rotated_outside, SIZE),
+        ("src pitch", lambda d: setattr(d, "src_pitch", w - 1), SIZE),
+        ("src frame stride", lambda d: setattr(d, "src_frame_stride", w * h - 1), SIZE),
+        ("gray pitch", lambda d: setattr(d, "gray_pitch", vw - 1), SIZE),
+        ("gray frame stride", lambda d: setattr(d, "gray_frame_stride", vw * vh - 1), SIZE),
+        ("rgb pitch", lambda d: setattr(d, "rgb_pitch", 3 * vw - 1), SIZE),
+        ("rgb frame stride", lambda d: setattr(d, "rgb_frame_stride", 3 * vw * vh - 1), SIZE),
+        ("null src", lambda d: setattr(d, "src", None), INV),
+        ("no output", both_null, INV),
+        ("gray on src", lambda d: setattr(d, "gray", src.data_ptr() + 100), INV),
+        ("rgb on src", lambda d: setattr(d, "rgb", src.data_ptr()), INV),
+        ("rgb on gray", lambda d: setattr(d, "rgb", gray.data_ptr() + vw), INV),
+    ]
+    for name, mutate, code in cases:
+        d = good()
+        mutate(d)
+        st = lib.d2pc_colorize_device(ctx._h, ctypes.byref(d), None)
+        assert st == code, (name, st)
+    assert lib.d2pc_colorize_device(ctx._h, None, None) == INV
+    assert lib.d2pc_colorize_device(None, ctypes.byref(good()), None) == INV
+    torch.cuda.synchronize()
+    assert (gray == 99).all() and (rgb == 99).all()  # nothing launched
+    for drop in (None, "gray", "rgb"):  # the good descriptor runs, with either output alone too
+        gray.fill_(99), rgb.fill_(99)
+        d = good()
+        if drop:
+            setattr(d, drop, None)
+        st = lib.d2pc_colorize_device(ctx._h, ctypes.byref(d), None)
+        torch.cuda.synchronize()
+        assert st == 0
+        assert (gray == (99 if drop == "gray" else 0)).all() and (rgb == (99 if drop == "rgb" else 0)).all()
+
+
+def test_graph_capture_and_replay(ctx):
+    rng = np.random.default_rng(8)
+    h, w = 480, 752
+    sq = d2pc.crop_to_square(h, w, 7, -15, 15)
+    static = torch.from_numpy(rng.integers(0, 256, size=(2, h, w)).astype(np.uint8)).cuda()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):  # warm-up outside the capture
+        colorize(ctx, static, sq, rotate_cw=True, want_gray=True)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):  # captures on a side stream of its own: one launch, no parallel branches
+        rgb, gray = colorize(ctx, static, sq, rotate_cw=True, want_gray=True)
+    for rep in range(3):
+        frames = rng.integers(0, 256, size=(2, h, w)).astype(np.uint8)
+        static.copy_(torch.from_numpy(frames))
+        g.replay()
+        torch.cuda.synchronize()
+        eager_rgb, eager_gray = colorize(ctx, static, sq, rotate_cw=True, want_gray=True)
+        torch.cuda.synchronize()
+        assert torch.equal(rgb, eager_rgb) and torch.equal(gray, eager_gray)
+        for k in range(2):
+            wr, wg = _want(frames[k], (sq[0], sq[1], sq[2], sq[2]), True)
+            assert np.array_equal(rgb[k].cpu().numpy(), wr) and np.array_equal(gray[k].cpu().numpy(), wg), (rep, k)
+
+
+def test_4k_batch_sampled(ctx):
+    """16 x 2160^2 views of 3840 x 2160 frames, rotated and not, checked on sampled frames."""
+    f, h, w = 16, 2160, 3840
+    frames = torch.randint(0, 256, (f, h, w), dtype=torch.uint8, device="cuda")
+    for rotate in (False, True):
+        sq = d2pc.crop_to_square(h, w) if rotate else d2pc.crop_to_square(w, h)
+        assert sq[2] == 2160
+        rgb, gray = colorize(ctx, frames, sq, rotate_cw=rotate, want_gray=True)
+        torch.cuda.synchronize()
+        for k in ((0, 15) if rotate else (7, 15)):
+            wr, wg = _want(frames[k].cpu().numpy(), (sq[0], sq[1], sq[2], sq[2]), rotate)
+            assert np.array_equal(gray[k].cpu().numpy(), wg), (rotate, k)
+            assert np.array_equal(rgb[k].cpu().numpy(), wr), (rotate, k)
+        del rgb, gray

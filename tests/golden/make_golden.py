@@ -20,72 +20,14 @@ Deterministic: fixed seeds, no dependence on the oracle or the product.
 """
 import json
 import os
-import struct
-from fractions import Fraction
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-FLT_MAX = np.float32(3.4028234663852886e38)
-
-
-def f32_bits(x: float) -> int:
-    return struct.unpack("<I", struct.pack("<f", x))[0]
-
-
-def round_fraction_to_f32(fr: Fraction) -> np.float32:
-    """Correctly rounded (nearest, ties-to-even) float32 of an exact rational."""
-    if fr == 0:
-        return np.float32(0.0)
-    # float(Fraction) is correctly rounded to float64; casting that to float32
-    # can double-round, so repair against the exact value.
-    c = np.float32(float(fr))
-    if not np.isfinite(c):
-        return c
-    lo = np.nextafter(c, np.float32(-np.inf))
-    hi = np.nextafter(c, np.float32(np.inf))
-    best = None
-    for cand in (lo, c, hi):
-        if not np.isfinite(cand):
-            continue
-        err = abs(Fraction(float(cand)) - fr)
-        key = (err, f32_bits(float(cand)) & 1)  # ties -> even mantissa
-        if best is None or key < best[0]:
-            best = (key, cand)
-    return best[1]
-
-
-def make_q_default(fx=714.24, fy=713.5, cx=376.0, cy=240.0, b=0.09, nx=752, ny=480):
-    """hpp:66-71,84-104 -- closed form of stereoRectify for the reference rig
-    (same formula as SURVEY.md section 8 row a9), evaluated in float64."""
-    fc = fy
-    hx, hy = (nx - 1) / 2.0, (ny - 1) / 2.0
-    cxn = hx - fc * (hx - cx) / fx
-    cyn = hy - fc * (hy - cy) / fy
-    tx = -b
-    return np.array(
-        [1, 0, 0, -cxn, 0, 1, 0, -cyn, 0, 0, 0, fc, 0, 0, -1.0 / tx, (cxn - cxn) / tx],
-        dtype=np.float64,
-    )
-
-
-def exact_points(q, disp, border, rows=None):
-    """Exact-rational reprojection of the ROI -> (R,4) uint32 bit patterns.
-    rows=(r0,r1) restricts the evaluation to image rows r0..r1-1."""
-    h, w = disp.shape
-    qf = [Fraction(float(v)) for v in q]
-    r0, r1 = rows if rows is not None else (border, h - border)
-    out = []
-    for v in range(r0, r1):
-        for u in range(border, w - border):
-            d = Fraction(float(disp[v, u]))
-            num = [qf[4 * r] * u + qf[4 * r + 1] * v + qf[4 * r + 2] * d + qf[4 * r + 3] for r in range(4)]
-            assert num[3] != 0, "exact W == 0: not a finite known-answer point"
-            xyz = [f32_bits(float(round_fraction_to_f32(num[r] / num[3]))) for r in range(3)]
-            if disp[v, u] == FLT_MAX:  # reprojectImageTo3D: |d - minDisparity| <= FLT_EPSILON => Z = bigZ = 10000,
-                xyz[2] = f32_bits(10000.0)  # minDisparity = FLT_MAX when handleMissingValues is false (cpp:64)
-            out.append(xyz + [0x3F800000])
-    return np.array(out, dtype=np.uint32).reshape(-1, 4)
+sys.path.insert(0, os.path.dirname(HERE))
+# the exact-rational evaluation itself lives in tests/exact_reproject.py, shared with the range tests
+from exact_reproject import FLT_MAX, exact_points, make_q_default  # noqa: E402
 
 
 def main():

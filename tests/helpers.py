@@ -13,16 +13,23 @@ def variant_for(algo=0, pxt=8, exp=False):
 DEFAULT_CALIB = dict(fx=714.24, fy=713.5, cx=376.0, cy=240.0, baseline=0.09, nx=752, ny=480)
 
 
+def line_bits(x):
+    """float32 values (or their uint32 bit patterns) on a monotone integer line: the position of a finite float is its
+    magnitude's bit pattern, negated for negative values, so that neighbouring floats are 1 apart and +-inf is the
+    position after +-FLT_MAX.  NaN has no meaningful position (callers mask it)."""
+    b = np.asarray(x)
+    b = (np.ascontiguousarray(b).view(np.uint32) if b.dtype == np.float32 else b.astype(np.uint32)).astype(np.int64)
+    mag = b & 0x7FFFFFFF
+    return np.where(b & 0x80000000 != 0, -mag, mag)
+
+
 def ulp_distance(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     """Distance in float32 ulps between finite values (0 when both are the
     same inf or both NaN; a huge number when the classes differ)."""
     a = np.ascontiguousarray(a, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
-    ai = a.view(np.int32).astype(np.int64)
-    bi = b.view(np.int32).astype(np.int64)
     # map the sign-magnitude float ordering onto a monotone integer line
-    ai = np.where(ai < 0, -(ai & 0x7FFFFFFF), ai)
-    bi = np.where(bi < 0, -(bi & 0x7FFFFFFF), bi)
+    ai, bi = line_bits(a), line_bits(b)
     d = np.abs(ai - bi)
     both_nan = np.isnan(a) & np.isnan(b)
     one_nan = np.isnan(a) ^ np.isnan(b)

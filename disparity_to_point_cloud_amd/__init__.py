@@ -54,6 +54,18 @@ from .capi import (  # noqa: F401
     ColorizeDesc,
     colorize_desc_init,
     colorize_table,
+    FusionNodeConfig,
+    FusionNodeGeometry,
+    FusionNodeTopics,
+    FusionNodeHostTopics,
+    FusionSession,
+    fusion_node_config_init,
+    fusion_node_geometry,
+    NODE_DISPARITY_1,
+    NODE_DISPARITY_2,
+    NODE_MATCHING_SCORE_1,
+    NODE_MATCHING_SCORE_2,
+    NODE_TOPICS,
 )
 
 

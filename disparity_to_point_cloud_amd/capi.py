@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "d2pc_median_roi_device", "d2pc_host_alloc", "d2pc_host_free", "d2pc_make_q_flavour",
     "d2pc_process_mono_device", "d2pc_set_reproject_form", "d2pc_score_filter_desc_init",
     "d2pc_score_filter_device", "d2pc_colorize_table", "d2pc_colorize_desc_init", "d2pc_colorize_device",
+    "d2pc_fusion_node_config_init", "d2pc_fusion_node_geometry", "d2pc_fusion_node_create", "d2pc_fusion_node_destroy",
+    "d2pc_fusion_node_callback_device", "d2pc_fusion_node_callback",
 ]
 # include/d2pc_ext.h: unstable, for bench.py / tools / tests only
 EXT_SYMBOLS = [
@@ -45,6 +47,10 @@ FORM_DEFAULT, FORM_CV24, FORM_CV4 = 0, 24, 4   # d2pc_reproject_form
 (FUSE_WEIGHTED_AVERAGE, FUSE_MAX_DIST, FUSE_MAX_DIST_UNLESS_BLACK, FUSE_BETTER_SCORE, FUSE_ONLY_GOOD_1,
  FUSE_ONLY_GOOD_AVG, FUSE_OVERLAP, FUSE_BLACK_TO_WHITE, FUSE_GRAD_FILTER) = range(9)
 SCORE_FORM_CV4, SCORE_FORM_CV3 = 4, 3  # d2pc_score_form
+NODE_DISPARITY_1, NODE_DISPARITY_2, NODE_MATCHING_SCORE_1, NODE_MATCHING_SCORE_2 = range(4)  # d2pc_fusion_node_callback_id
+# d2pc_fusion_node_topic_id, in the order of the reference's publishers
+NODE_TOPICS = ("cropped_depth_1", "cropped_depth_2", "cropped_score_1", "cropped_score_2", "fused_depth_map",
+               "combined_score", "gradient")
 
 
 class Config(ctypes.Structure):
@@ -110,6 +116,43 @@ class ColorizeDesc(ctypes.Structure):
         ("src", ctypes.c_void_p), ("src_pitch", ctypes.c_size_t), ("src_frame_stride", ctypes.c_size_t),
         ("gray", ctypes.c_void_p), ("gray_pitch", ctypes.c_size_t), ("gray_frame_stride", ctypes.c_size_t),
         ("rgb", ctypes.c_void_p), ("rgb_pitch", ctypes.c_size_t), ("rgb_frame_stride", ctypes.c_size_t),
+    ]
+
+
+class FusionNodeConfig(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("cols", ctypes.c_int32), ("rows", ctypes.c_int32),
+        ("offset_x", ctypes.c_int32), ("offset_y", ctypes.c_int32), ("rule", ctypes.c_int32),
+        ("score_form", ctypes.c_int32), ("batch", ctypes.c_int32), ("crop_left", ctypes.c_int32),
+        ("crop_right", ctypes.c_int32), ("crop_top", ctypes.c_int32), ("crop_bottom", ctypes.c_int32),
+        ("single_launch", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class FusionNodeGeometry(ctypes.Structure):
+    _fields_ = [
+        ("x1", ctypes.c_int32), ("y1", ctypes.c_int32), ("x2", ctypes.c_int32), ("y2", ctypes.c_int32),
+        ("n", ctypes.c_int32), ("fused_width", ctypes.c_int32), ("fused_height", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("topic_bytes", ctypes.c_size_t * 7),
+    ]
+
+
+class FusionNodeTopic(ctypes.Structure):
+    _fields_ = [
+        ("data", ctypes.c_void_p), ("pitch", ctypes.c_size_t), ("frame_stride", ctypes.c_size_t),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("channels", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class FusionNodeTopics(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("published", ctypes.c_uint32), ("topic", FusionNodeTopic * 7)]
+
+
+class FusionNodeHostTopics(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("published", ctypes.c_uint32), ("data", ctypes.c_void_p * 7),
+        ("capacity", ctypes.c_size_t * 7), ("bytes", ctypes.c_size_t * 7), ("width", ctypes.c_int32 * 7),
+        ("height", ctypes.c_int32 * 7), ("channels", ctypes.c_int32 * 7),
     ]
 
 
@@ -270,6 +313,14 @@ def load_library(variant=None):
     L.d2pc_colorize_desc_init.argtypes = [ctypes.POINTER(ColorizeDesc)]
     L.d2pc_colorize_desc_init.restype = None
     L.d2pc_colorize_device.argtypes = [vp, ctypes.POINTER(ColorizeDesc), vp]
+    L.d2pc_fusion_node_config_init.argtypes = [ctypes.POINTER(FusionNodeConfig)]
+    L.d2pc_fusion_node_config_init.restype = None
+    L.d2pc_fusion_node_geometry.argtypes = [ctypes.POINTER(FusionNodeConfig), ctypes.POINTER(FusionNodeGeometry)]
+    L.d2pc_fusion_node_create.argtypes = [vp, ctypes.POINTER(FusionNodeConfig), ctypes.POINTER(vp)]
+    L.d2pc_fusion_node_destroy.argtypes = [vp]
+    L.d2pc_fusion_node_callback_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                                   ctypes.POINTER(FusionNodeTopics), vp]
+    L.d2pc_fusion_node_callback.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(FusionNodeHostTopics)]
     L.d2pc_crop_to_square.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 3
     L.d2pc_check_async_error.argtypes = [vp]
     L.d2pc_reserve_mono.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -703,3 +754,155 @@ def crop_to_square(cols, rows, offset_x=0, offset_y=0, member_offset_y=None):
     if st != 0:
         raise D2pcError(st, "crop_to_square(%d,%d,%d,%d)" % (cols, rows, offset_x, offset_y))
     return x.value, y.value, n.value
+
+
+def fusion_node_config_init(**kw) -> FusionNodeConfig:
+    """d2pc_fusion_node_config_init, then the given fields."""
+    c = FusionNodeConfig()
+    load_library().d2pc_fusion_node_config_init(ctypes.byref(c))
+    for k, v in kw.items():
+        if k not in dict(FusionNodeConfig._fields_):
+            raise TypeError("d2pc_fusion_node_config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def fusion_node_geometry(cfg: FusionNodeConfig) -> FusionNodeGeometry:
+    """d2pc_fusion_node_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = FusionNodeGeometry()
+    st = load_library().d2pc_fusion_node_geometry(ctypes.byref(cfg), ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "fusion_node_geometry(%dx%d, %d/%d)" % (cfg.cols, cfg.rows, cfg.offset_x, cfg.offset_y))
+    return g
+
+
+class _DeviceView:
+    """A topic buffer of the C session for torch.as_tensor (the CUDA array interface); keeps the session alive."""
+
+    def __init__(self, owner, ptr, shape, strides):
+        self.owner = owner
+        self.__cuda_array_interface__ = {"shape": shape, "strides": strides, "typestr": "|u1", "data": (ptr, False),
+                                         "version": 2}
+
+
+class FusionSession:
+    """d2pc_fusion_node_* (the depth_map_fusion node as a session of the C ABI) with FusionNode's interface: the four
+    callbacks take uint8 CUDA tensors of shape (rows, cols) -- (batch, rows, cols) for batch > 1 -- and return
+    {topic: tensor}, the tensors being VIEWS of the session's own device buffers (no copy); the `*_host` forms take
+    and return numpy arrays through the synchronous d2pc_fusion_node_callback.  The aliasing rules are FusionNode's."""
+
+    def __init__(self, ctx: "Context", cols, rows, offset_x=0, offset_y=0, rule=FUSE_GRAD_FILTER, form=SCORE_FORM_CV4,
+                 batch=1, single_launch=None, crop=None):
+        self._L, self.ctx = ctx._L, ctx
+        kw = dict(cols=cols, rows=rows, offset_x=offset_x, offset_y=offset_y, rule=rule, score_form=form, batch=batch)
+        if single_launch is not None:
+            kw["single_launch"] = int(single_launch)
+        if crop is not None:
+            kw["crop_left"], kw["crop_right"], kw["crop_top"], kw["crop_bottom"] = crop
+        self.cfg = fusion_node_config_init(**kw)
+        self._h = None
+        h = ctypes.c_void_p()
+        st = self._L.d2pc_fusion_node_create(ctx.handle, ctypes.byref(self.cfg), ctypes.byref(h))
+        if st:
+            raise D2pcError(st, self._L.d2pc_last_error(ctx.handle).decode())
+        self._h = h
+        g = self.geometry = fusion_node_geometry(self.cfg)
+        self.cols, self.rows, self.batch, self.n = int(cols), int(rows), int(batch), g.n
+        self.sq1, self.sq2 = (g.x1, g.y1, g.n), (g.x2, g.y2, g.n)
+        self.fused_w, self.fused_h = g.fused_width, g.fused_height
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.d2pc_fusion_node_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, st):
+        if st:
+            raise D2pcError(st, self._L.d2pc_last_error(self.ctx.handle).decode())
+
+    # -- device entry ---------------------------------------------------------------------------------------------
+    def callback_device(self, which, d_frame_ptr, pitch, frame_stride=0, stream_ptr=None) -> FusionNodeTopics:
+        """d2pc_fusion_node_callback_device on raw pointers."""
+        out = FusionNodeTopics()
+        out.struct_size = ctypes.sizeof(FusionNodeTopics)
+        self._check(self._L.d2pc_fusion_node_callback_device(self._h, which, d_frame_ptr, pitch, frame_stride,
+                                                             ctypes.byref(out), stream_ptr))
+        return out
+
+    def _views(self, out):
+        import torch
+
+        views = {}
+        for i, name in enumerate(NODE_TOPICS):
+            if not (out.published >> i) & 1:
+                continue
+            t = out.topic[i]
+            shape = (self.batch, t.height, t.width) + ((t.channels,) if t.channels > 1 else ())
+            strides = (t.frame_stride, t.pitch, t.channels) + ((1,) if t.channels > 1 else ())
+            v = torch.as_tensor(_DeviceView(self, t.data, shape, strides), device="cuda")
+            views[name] = v[0] if self.batch == 1 else v
+        return views
+
+    def _call(self, which, frame):
+        import torch
+
+        want = (self.rows, self.cols) if self.batch == 1 else (self.batch, self.rows, self.cols)
+        if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8:
+            raise ValueError("frame must be a uint8 CUDA tensor")
+        if self.batch == 1 and frame.dim() == 3 and frame.shape[0] == 1:
+            frame = frame[0]
+        if tuple(frame.shape) != want or frame.stride(-1) != 1:
+            raise ValueError("frame of shape %s: %s with unit column stride expected" % (tuple(frame.shape), want))
+        fstride = frame.stride(0) if frame.dim() == 3 else 0
+        stream = torch.cuda.current_stream(frame.device).cuda_stream
+        return self._views(self.callback_device(which, frame.data_ptr(), frame.stride(-2), fstride, stream))
+
+    def disparity_1(self, frame):
+        return self._call(NODE_DISPARITY_1, frame)
+
+    def disparity_2(self, frame):
+        return self._call(NODE_DISPARITY_2, frame)
+
+    def matching_score_1(self, frame):
+        return self._call(NODE_MATCHING_SCORE_1, frame)
+
+    def matching_score_2(self, frame):
+        return self._call(NODE_MATCHING_SCORE_2, frame)
+
+    # -- host entry -----------------------------------------------------------------------------------------------
+    def callback_host(self, which, frame: np.ndarray, capacity=None):
+        """d2pc_fusion_node_callback: numpy uint8 frame(s) in, {topic: numpy array} out.  `capacity` = {topic: bytes}
+        shrinks the buffers offered for those topics (tests of D2PC_ERR_CAPACITY)."""
+        want = (self.rows, self.cols) if self.batch == 1 else (self.batch, self.rows, self.cols)
+        if frame.dtype != np.uint8 or frame.shape != want or frame.strides[-1] != 1:
+            raise ValueError("frame of shape %s / dtype %s: uint8 %s expected" % (frame.shape, frame.dtype, want))
+        if frame.ndim == 3 and frame.strides[0] != frame.strides[1] * self.rows:
+            frame = np.ascontiguousarray(frame)
+        io = FusionNodeHostTopics()
+        io.struct_size = ctypes.sizeof(FusionNodeHostTopics)
+        bufs = []
+        for i, name in enumerate(NODE_TOPICS):
+            b = np.empty(max(int(self.geometry.topic_bytes[i]), 1), dtype=np.uint8)
+            bufs.append(b)
+            io.data[i] = b.ctypes.data
+            io.capacity[i] = b.size if not capacity or name not in capacity else capacity[name]
+        self._check(self._L.d2pc_fusion_node_callback(self._h, which, frame.ctypes.data, frame.strides[-2], ctypes.byref(io)))
+        out = {}
+        for i, name in enumerate(NODE_TOPICS):
+            if (io.published >> i) & 1:
+                shape = (self.batch, io.height[i], io.width[i]) + ((io.channels[i],) if io.channels[i] > 1 else ())
+                a = bufs[i][: io.bytes[i]].reshape(shape)
+                out[name] = a[0] if self.batch == 1 else a
+        return out

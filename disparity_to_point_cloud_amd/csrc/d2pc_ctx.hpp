@@ -7,6 +7,7 @@
 //   d2pc_capi_host.hip     the synchronous host entry points (d2pc_process*) and the pipelined host path (d2pc_pipeline_*)
 //   d2pc_capi_mono.hip     cv_bridge rescale, median, the device-resident callback body (d2pc_process_mono_device)
 //   d2pc_capi_fusion.hip   depth-map fusion inner loop, rotate, crop
+//   d2pc_capi_node.hip     the depth_map_fusion node as a session (d2pc_fusion_node_*)
 //   d2pc_capi_ext.hip      include/d2pc_ext.h: tuning keys, test hooks, device calibration kernels
 // Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol).
 #pragma once

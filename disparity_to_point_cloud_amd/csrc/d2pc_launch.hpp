@@ -129,6 +129,31 @@ hipError_t launch_colorize(ColorizeArgs a, hipStream_t stream);
 // The table itself (host): row g is bytes 3g .. 3g + 2.
 void colorize_table(uint8_t table[768]);
 
+// The fusing DisparityCb2 of the node session in ONE launch (d2pc_node.hip): camera 2's raw frame
+// through the rotated, cropped view -> its colouring; GRAD_FILTER fusion with camera 1's depth and the two score planes;
+// min(grad1, grad2); 3x3 median; crop; the fused map and its colouring.  All planes are n x n unless noted.
+struct NodeFuseArgs {
+  const uint8_t *frame2 = nullptr;        // camera 2's raw frame(s): `rows` rows as stored
+  const uint8_t *depth1 = nullptr, *score1 = nullptr, *score2 = nullptr;
+  uint8_t *spare = nullptr;               // out: min(score1, score2)  (score and grad of a camera are one plane)
+  uint8_t *rgb2 = nullptr;                // out: n x n x 3, colouring of camera 2's view
+  uint8_t *fused = nullptr;               // out: out_width x out_height
+  uint8_t *gradient = nullptr;            // out: out_width x out_height x 3
+  const uint32_t *table = nullptr;        // DEVICE: 256 colour entries, byte0 | byte1 << 8 | byte2 << 16
+  uint64_t frame2_pitch = 0, frame2_frame_stride = 0;
+  uint64_t depth1_pitch = 0, score1_pitch = 0, score2_pitch = 0, spare_pitch = 0, rgb2_pitch = 0, fused_pitch = 0,
+           gradient_pitch = 0;
+  uint64_t depth1_frame_stride = 0, score1_frame_stride = 0, score2_frame_stride = 0, spare_frame_stride = 0,
+           rgb2_frame_stride = 0, fused_frame_stride = 0, gradient_frame_stride = 0;
+  int32_t rows = 0;                       // of the raw frame
+  int32_t x2 = 0, y2 = 0, n = 0;          // camera 2's square in the ROTATED frame
+  int32_t crop_left = 0, crop_top = 0, out_width = 0, out_height = 0;
+  int32_t n_frames = 1;
+  uint32_t tiles_x = 0, tiles_y = 0;      // filled by launch_node_fuse
+};
+// tile_rows: 0 = choose (16 rows until the launch has 2048 tiles of 64 rows, then 64), else 16 or 64
+hipError_t launch_node_fuse(NodeFuseArgs a, hipStream_t stream, int tile_rows = 0);
+
 bool tile_shape_supported(int pxt);
 uint32_t frame_state_stride(uint32_t tiles_per_frame);
 size_t compact_state_bytes(const Geom &g);

@@ -18,6 +18,13 @@
 //        D2PC_ERR_CAPACITY -- logged, frame dropped; border 40 again, frame 3 is published and written to <out.bin>
 //   d2pc_replay latency <in.raw> <w> <h> <mono8|mono16> <frames> [compact] [pinned]
 //        per-frame wall time of DisparityCb over <frames> calls (median, p10, p90 in microseconds)
+//   d2pc_replay fusion <script> <w> <h> <mono8|mono16> <out_prefix> [offset_x=N] [offset_y=N] [single_launch=0|1]
+//        the depth_map_fusion node (host/depth_map_fusion_amd.hpp): every line of <script> is one callback,
+//            D1|D2|S1|S2 <raw frame file> [<w> <h>]      (# starts a comment; paths are relative to the script)
+//        DisparityCb1/2, MatchingScoreCb1/2 in that order through ONE node; message i (from 0) it publishes goes to
+//        <out_prefix>.<i>.raw and one line of <out_prefix>.index: i, script line, topic, width, height, encoding, step,
+//        frame_id, stamp, bytes; the last line of the index is "dropped <frames>".  A malformed script, an unreadable or
+//        short frame file: exit 2 before any device is touched
 //   d2pc_replay --gpus N | --device D [...]
 //        the multi-GPU deployment in one process: RCCL broadcast of the calibration, one thread + context + frame
 //        queue per GPU, counters all-reduced (host/multi_gpu.hpp)
@@ -31,7 +38,9 @@
 #include <fstream>
 #include <iostream>
 #include <memory>
+#include <sstream>
 
+#include "depth_map_fusion_amd.hpp"
 #include "disparity_to_point_cloud_amd.hpp"
 #include "multi_gpu.hpp"
 #include "ros_shim.hpp"
@@ -108,6 +117,82 @@ static int run_latency(int argc, char **argv, const std::shared_ptr<d2pc_shim::I
   return 0;
 }
 
+// d2pc_replay fusion: see the head of this file
+static int run_fusion(int argc, char **argv) {
+  struct Step { int line; std::string cb; std::shared_ptr<d2pc_shim::Image> img; };
+  const std::string script = argv[2], enc = argv[5], prefix = argv[6];
+  const int w0 = atoi(argv[3]), h0 = atoi(argv[4]);
+  if (w0 <= 0 || h0 <= 0 || (enc != "mono8" && enc != "mono16")) { fprintf(stderr, "fusion: bad frame size or encoding\n"); return 2; }
+  std::ifstream in(script);
+  if (!in) { fprintf(stderr, "fusion: cannot read script %s\n", script.c_str()); return 2; }
+  const size_t slash = script.find_last_of('/');
+  const std::string dir = slash == std::string::npos ? "" : script.substr(0, slash + 1);
+  std::vector<Step> steps;
+  std::string text;
+  for (int line = 1; std::getline(in, text); ++line) {
+    const size_t hash = text.find('#');
+    if (hash != std::string::npos) text.erase(hash);
+    std::istringstream ls(text);
+    std::string cb, path, extra;
+    if (!(ls >> cb)) continue;  // blank
+    int w = w0, h = h0;
+    if (cb != "D1" && cb != "D2" && cb != "S1" && cb != "S2") { fprintf(stderr, "fusion: line %d: unknown callback '%s'\n", line, cb.c_str()); return 2; }
+    if (!(ls >> path)) { fprintf(stderr, "fusion: line %d: no frame file\n", line); return 2; }
+    if (ls >> extra) {  // an explicit size: both numbers, positive, nothing behind them
+      std::string hs, more;
+      if (!(ls >> hs) || (ls >> more) || (w = atoi(extra.c_str())) <= 0 || (h = atoi(hs.c_str())) <= 0) {
+        fprintf(stderr, "fusion: line %d: expected '<w> <h>' behind the file\n", line);
+        return 2;
+      }
+    }
+    std::ifstream f((path[0] == '/' ? path : dir + path).c_str(), std::ios::binary);
+    if (!f) { fprintf(stderr, "fusion: line %d: cannot read %s\n", line, path.c_str()); return 2; }
+    auto img = std::make_shared<d2pc_shim::Image>();
+    img->data.assign(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+    img->width = uint32_t(w), img->height = uint32_t(h), img->encoding = enc;
+    img->step = img->width * (enc == "mono16" ? 2u : 1u);
+    if (img->data.size() != size_t(img->step) * img->height) {
+      fprintf(stderr, "fusion: line %d: %s holds %zu bytes, %ux%u %s needs %zu\n", line, path.c_str(), img->data.size(), img->width,
+              img->height, enc.c_str(), size_t(img->step) * img->height);
+      return 2;
+    }
+    img->header.seq = uint32_t(line);
+    img->header.stamp.sec = 1000u + uint32_t(line);
+    img->header.stamp.nsec = 7u * uint32_t(line);
+    img->header.frame_id = "cam_" + cb;
+    steps.push_back(Step{line, cb, img});
+  }
+  if (steps.empty()) { fprintf(stderr, "fusion: the script holds no callback\n"); return 2; }
+  d2pc::FusionParamSource nh;
+  int single = -1;
+  for (int i = 7; i < argc; ++i) {
+    if (!strncmp(argv[i], "offset_x=", 9)) nh.values["offset_x"] = atoi(argv[i] + 9);
+    if (!strncmp(argv[i], "offset_y=", 9)) nh.values["offset_y"] = atoi(argv[i] + 9);
+    if (!strncmp(argv[i], "single_launch=", 14)) single = atoi(argv[i] + 14);
+  }
+  std::ofstream index((prefix + ".index").c_str());
+  int n_msg = 0, line_now = 0;
+  d2pc::DepthMapFusionT<d2pc_shim::Msgs> node(
+      nh,
+      [&](const char *topic, const d2pc_shim::Image &m) {
+        index << n_msg << " " << line_now << " " << topic << " " << m.width << " " << m.height << " " << m.encoding << " " << m.step << " "
+              << m.header.frame_id << " " << m.header.stamp.sec << "." << m.header.stamp.nsec << " " << m.data.size() << "\n";
+        std::ofstream((prefix + "." + std::to_string(n_msg) + ".raw").c_str(), std::ios::binary)
+            .write(reinterpret_cast<const char *>(m.data.data()), std::streamsize(m.data.size()));
+        ++n_msg;
+      },
+      device_from(argc, argv), single);
+  for (const Step &s : steps) {
+    line_now = s.line;
+    if (s.cb == "D1") node.DisparityCb1(s.img);
+    else if (s.cb == "D2") node.DisparityCb2(s.img);
+    else if (s.cb == "S1") node.MatchingScoreCb1(s.img);
+    else node.MatchingScoreCb2(s.img);
+  }
+  index << "dropped " << node.frames_dropped() << "\n";
+  return 0;
+}
+
 int main(int argc, char **argv) {
   {
     const d2pc_multi::Options mo = d2pc_multi::parse(argc, argv);
@@ -115,6 +200,14 @@ int main(int argc, char **argv) {
   }
   if (argc < 7) { fprintf(stderr, "usage: see replay_main.cpp\n"); return 2; }
   const std::string cmd = argv[1], enc = argv[5];
+  if (cmd == "fusion") {
+    try {
+      return run_fusion(argc, argv);
+    } catch (const std::exception &e) {
+      fprintf(stderr, "exception: %s\n", e.what());
+      return 4;
+    }
+  }
   auto img = std::make_shared<d2pc_shim::Image>();
   img->width = uint32_t(atoi(argv[3]));
   img->height = uint32_t(atoi(argv[4]));

@@ -549,6 +549,112 @@ void d2pc_colorize_desc_init(d2pc_colorize_desc *desc);
  * as it is.  At least one output; outputs must not overlap the source or each other. */
 int d2pc_colorize_device(d2pc_ctx *ctx, const d2pc_colorize_desc *desc, void *stream);
 
+/*
+ * The depth_map_fusion node (src/depth_map_fusion.cpp) as a SESSION: the four callbacks, the state they share and the
+ * seven topics they publish, for `batch` independent camera pairs.  The node owns every plane on its context's device
+ * (two depth planes, camera 1's score plane and a spare, camera 2's score plane and its rotated frame, two colour
+ * images, the fused map and its colouring); everything is allocated by d2pc_fusion_node_create, so a callback is a
+ * fixed sequence of kernel launches: no allocation, no device-to-device copy.
+ *
+ * The reference keeps camera 1's score, its grad and the combined confidence in ONE buffer (:77,:113): each fusion
+ * leaves min(grad1, grad2) in camera 1's score plane until the next matching-score-1 callback, and a disparity-2
+ * callback without new scores fuses against that.  The node reproduces this by swapping the score plane with the
+ * spare, never by copying; which is which is HOST state.  So the COMBINED_SCORE and CROPPED_SCORE_1 buffers are
+ * additionally overwritten by the next MATCHING_SCORE_1 / DISPARITY_2 callback; every other topic's buffer by the next
+ * callback that publishes that topic.
+ */
+typedef enum d2pc_fusion_node_callback_id {
+  D2PC_NODE_DISPARITY_1 = 0,        /* DisparityCb1 (:45-51)      publishes CROPPED_DEPTH_1 */
+  D2PC_NODE_DISPARITY_2 = 1,        /* DisparityCb2 (:53-61)      CROPPED_DEPTH_2 and, once all four planes have arrived
+                                       (:106-109), COMBINED_SCORE, GRADIENT, FUSED_DEPTH_MAP */
+  D2PC_NODE_MATCHING_SCORE_1 = 2,   /* MatchingScoreCb1 (:64-80)  CROPPED_SCORE_1 */
+  D2PC_NODE_MATCHING_SCORE_2 = 3    /* MatchingScoreCb2 (:82-99)  CROPPED_SCORE_2 */
+} d2pc_fusion_node_callback_id;
+
+/* Topics, in the order of the reference's publishers; bit (1 << id) of a `published` mask. */
+typedef enum d2pc_fusion_node_topic_id {
+  D2PC_TOPIC_CROPPED_DEPTH_1 = 0,   /* n x n x 3 */
+  D2PC_TOPIC_CROPPED_DEPTH_2 = 1,   /* n x n x 3 */
+  D2PC_TOPIC_CROPPED_SCORE_1 = 2,   /* n x n */
+  D2PC_TOPIC_CROPPED_SCORE_2 = 3,   /* n x n */
+  D2PC_TOPIC_FUSED_DEPTH_MAP = 4,   /* fused_width x fused_height */
+  D2PC_TOPIC_COMBINED_SCORE = 5,    /* n x n */
+  D2PC_TOPIC_GRADIENT = 6           /* fused_width x fused_height x 3 */
+} d2pc_fusion_node_topic_id;
+#define D2PC_NODE_TOPICS 7
+
+typedef struct d2pc_fusion_node_config {
+  uint32_t struct_size;        /* sizeof(d2pc_fusion_node_config) */
+  int32_t cols, rows;          /* of every incoming frame */
+  int32_t offset_x, offset_y;  /* the node's params (:119-124) */
+  int32_t rule;                /* d2pc_fusion_rule */
+  int32_t score_form;          /* d2pc_score_form */
+  int32_t batch;               /* independent camera pairs per callback */
+  int32_t crop_left, crop_right, crop_top, crop_bottom;   /* cropMat of publishFusedDepthMap (:130) */
+  int32_t single_launch;       /* 1: a fusing DISPARITY_2 with rule GRAD_FILTER is ONE kernel launch; 0: always the
+                                  three-launch composition.  Same bytes either way.  One launch is 3 x faster for one
+                                  camera frame, level at 16 and slower beyond: large batches set 0. */
+  int32_t reserved[3];
+} d2pc_fusion_node_config;
+
+/* struct_size; offsets 0/0 (the class defaults, hpp:92-93); GRAD_FILTER (:159); D2PC_SCORE_FORM_CV4; batch 1; crop
+ * 0/40/30/10 (:130); single_launch 1; cols = rows = 0: the caller's to set. */
+void d2pc_fusion_node_config_init(d2pc_fusion_node_config *cfg);
+
+typedef struct d2pc_fusion_node_geometry_t {
+  int32_t x1, y1;              /* camera 1's square: cropToSquare(frame, offset_x, offset_y) */
+  int32_t x2, y2;              /* camera 2's, in the ROTATED frame: cropToSquare(rotated, -offset_x, -offset_y), its
+                                  side from the member offset_y (:253) */
+  int32_t n;                   /* side of both */
+  int32_t fused_width, fused_height;
+  int32_t reserved;
+  size_t topic_bytes[D2PC_NODE_TOPICS];  /* bytes of each topic's image, all `batch` pairs together */
+} d2pc_fusion_node_geometry_t;
+
+/* Host arithmetic only (no context, no device).  D2PC_ERR_BAD_SIZE when a square leaves its frame, the two squares
+ * differ in size, n < 11 (the score filter's halo) or the crop leaves nothing of the fused map. */
+int d2pc_fusion_node_geometry(const d2pc_fusion_node_config *cfg, d2pc_fusion_node_geometry_t *out);
+
+typedef struct d2pc_fusion_node d2pc_fusion_node;
+/* The node lives on `ctx`'s device and must be destroyed before the context. */
+int d2pc_fusion_node_create(d2pc_ctx *ctx, const d2pc_fusion_node_config *cfg, d2pc_fusion_node **out);
+int d2pc_fusion_node_destroy(d2pc_fusion_node *node);
+
+typedef struct d2pc_fusion_node_topic {
+  void *data;                  /* DEVICE: the node's own buffer */
+  size_t pitch, frame_stride;  /* bytes between rows / between the pairs of a batch */
+  int32_t width, height, channels, reserved;
+} d2pc_fusion_node_topic;
+typedef struct d2pc_fusion_node_topics {
+  uint32_t struct_size;        /* sizeof(d2pc_fusion_node_topics), set by the caller */
+  uint32_t published;          /* out: bit (1 << d2pc_fusion_node_topic_id) per topic this call published */
+  d2pc_fusion_node_topic topic[D2PC_NODE_TOPICS];  /* out: filled for the published topics, zero otherwise */
+} d2pc_fusion_node_topics;
+
+/* One callback on frames resident on the device: `batch` mono8 frames of cols x rows, `frame_stride` bytes apart
+ * (ignored for batch 1), rows `pitch` bytes apart.  Asynchronous on `stream` (NULL = the HIP default stream).
+ * Capturable into a graph; a captured callback is pinned to the planes it was captured with, so capture
+ * MATCHING_SCORE_1 and DISPARITY_2 together (the pair replays exactly as the eager node runs it), not a fusing
+ * DISPARITY_2 alone.  The frame must not overlap the node's buffers. */
+int d2pc_fusion_node_callback_device(d2pc_fusion_node *node, int which, const void *d_frame, size_t pitch,
+                                     size_t frame_stride, d2pc_fusion_node_topics *out, void *stream);
+
+typedef struct d2pc_fusion_node_host_topics {
+  uint32_t struct_size;               /* sizeof(d2pc_fusion_node_host_topics), set by the caller */
+  uint32_t published;                 /* out: as above */
+  void *data[D2PC_NODE_TOPICS];       /* in: HOST buffer per topic, rows packed (step = width x channels); NULL =
+                                         do not copy that topic */
+  size_t capacity[D2PC_NODE_TOPICS];  /* in: bytes each buffer holds */
+  size_t bytes[D2PC_NODE_TOPICS];     /* out: bytes of each published topic (all pairs), copied unless data is NULL */
+  int32_t width[D2PC_NODE_TOPICS], height[D2PC_NODE_TOPICS], channels[D2PC_NODE_TOPICS];  /* out */
+} d2pc_fusion_node_host_topics;
+
+/* The same for frames in HOST memory (mono8, `batch` frames packed pitch x rows apart), synchronous: upload, the
+ * launches, download of the published topics.  A non-NULL buffer smaller than its topic gives D2PC_ERR_CAPACITY
+ * BEFORE anything is enqueued: the node's state is as it was and the node stays usable. */
+int d2pc_fusion_node_callback(d2pc_fusion_node *node, int which, const void *host_frame, size_t pitch,
+                              d2pc_fusion_node_host_topics *io);
+
 #ifdef __cplusplus
 }
 #endif

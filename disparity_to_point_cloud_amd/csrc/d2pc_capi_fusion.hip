@@ -215,6 +215,7 @@ int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, 
   a.width = d.width, a.height = d.height, a.x0 = d.x, a.y0 = d.y, a.n = d.n, a.n_frames = d.n_frames;
   a.direction = d.direction;
   a.form = d.form;
+  a.tile = ctx->score_tile;
   D2PC_HIP(ctx, launch_score_filter(a, static_cast<hipStream_t>(stream)));
   return D2PC_OK;
 }

@@ -139,6 +139,7 @@ struct d2pc_ctx {
   d2pc_stage_times times{};
   bool have_times = false;
   int fuse_rows = 0;             // d2pc_fuse_device rows per wave: 0 = choose, else 2..1024
+  int score_tile = 0;            // d2pc_score_filter_device tile edge: 0 = choose per launch (launch_score_filter), 32, 64
   int host_direct_read = 1;      // synchronous host entry points: a PINNED input frame is read by the first kernel in place
   int median_algo = 0;           // MedianArgs::algo: 0 choose per launch, 1 per-pixel select, 2 bit-sliced (k = 9, 11)
   // device scratch

@@ -108,6 +108,7 @@ struct ScoreArgs {
   int32_t width = 0, height = 0, x0 = 0, y0 = 0, n = 0, n_frames = 1;
   int32_t direction = 0, form = 4;
   int32_t t13[13] = {}, t21[21] = {};
+  int32_t tile = 0;   // 0: choose per launch, 32 / 64: force the tile (tuning key score_tile)
   int32_t tiles = 0;  // filled by launch_score_filter
 };
 hipError_t launch_score_filter(ScoreArgs a, hipStream_t stream);

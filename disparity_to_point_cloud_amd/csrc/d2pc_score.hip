@@ -245,7 +245,8 @@ hipError_t launch_score_filter(ScoreArgs a, hipStream_t stream) {
   }
   // 64 x 64 tiles (halo recompute x2 in A); 32 x 32 when that leaves most CUs idle (one 465 x 465 frame)
   const int t64 = (a.n + 63) / 64;
-  if (uint64_t(t64) * t64 * a.n_frames >= 512) {
+  if (a.tile != 0 && a.tile != 32 && a.tile != 64) return hipErrorInvalidValue;
+  if (a.tile ? a.tile == 64 : uint64_t(t64) * t64 * a.n_frames >= 512) {
     a.tiles = t64;
     return launch_tile<64>(a, stream);
   }

@@ -113,7 +113,9 @@ int d2pc_last_stage_times(d2pc_ctx *ctx, d2pc_stage_times *times);
  * "membench_nt" (0/1), "host_direct_read" (0/1, default 1: a pinned fp32 / 8-bit frame handed to d2pc_process /
  * d2pc_process_mono8 without a median is read by the reprojection in place, PARITY mode), "median_algo" (0 = choose
  * per launch, 1 = one pixel per thread, 2 = 32 pixels per thread, bit-sliced; the two give identical bytes),
- * "onepass_form" (0 = choose, 2 = the dense single pass: the only form of the product).
+ * "onepass_form" (0 = choose, 2 = the dense single pass: the only form of the product), "score_tile" (tile edge of
+ * d2pc_score_filter_device and of the session's MATCHING_SCORE callbacks: 0 = choose per launch -- 64 when the launch
+ * has at least 512 such tiles, else 32 -- the default; 32 or 64 force it; any other value is refused).
  * (Closed in round 6 and moved to the experiment build: "resident_pair" -- two 4K-class COMPACT frames in one call: 0 = one
  * launch each (the product), 1 = round 4's one launch of blocks twice the size -- and "resident_stagger_pct", the scale of
  * the resident blocks' ramped start: profiles/r04_ab_stagger.txt, r05_ab_pair.txt.)

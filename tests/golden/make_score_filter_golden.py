@@ -12,7 +12,7 @@ in exact rational arithmetic, one rounding per stage --
   * out = min(255, S + 2 B).
 
 The tap tables come from tests/score_filter_ref.py (the fp64 derivation) and are stored beside the cases.
-Run:  python tests/golden/make_score_filter_golden.py   (pure python + numpy, ~10 s) -> score_filter.npz
+Run:  python tests/golden/make_score_filter_golden.py   (pure python + numpy, a few minutes) -> score_filter.npz
 """
 import os
 import sys
@@ -94,6 +94,8 @@ def cases():
     yield "tiny", rng.integers(0, 256, size=(11, 14)).astype(np.uint8), (2, 0, 11)  # n = 11: the smallest square
     f, sq = tie_frame(rng)
     yield "g13_tie", f, sq
+    from score_patterns import golden_crops  # crops of the value patterns: no blind spot shared by restatement and kernel
+    yield from golden_crops()
 
 
 def main():

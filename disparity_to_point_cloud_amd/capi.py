@@ -776,6 +776,36 @@ def fusion_node_geometry(cfg: FusionNodeConfig) -> FusionNodeGeometry:
     return g
 
 
+def _frame_shape(rows, cols, batch):
+    return (rows, cols) if batch == 1 else (batch, rows, cols)
+
+
+def device_frames(frame, rows, cols, batch):
+    """The frame(s) a fusion callback takes, checked: a uint8 CUDA tensor of shape (rows, cols) -- (batch, rows, cols) for
+    batch > 1 -- with unit column stride (a leading axis of one is dropped for batch 1).  ValueError otherwise."""
+    import torch
+
+    if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8:
+        raise ValueError("frame must be a uint8 (mono8) CUDA tensor")
+    if batch == 1 and frame.dim() == 3 and frame.shape[0] == 1:
+        frame = frame[0]
+    want = _frame_shape(rows, cols, batch)
+    if tuple(frame.shape) != want or frame.stride(-1) != 1:
+        raise ValueError("frame of shape %s: %s with unit column stride expected" % (tuple(frame.shape), want))
+    return frame
+
+
+def host_frames(frame: np.ndarray, rows, cols, batch):
+    """The numpy form: uint8, (rows, cols) or (batch, rows, cols), unit column stride, or ValueError; a batch whose frames
+    are not one plane apart is copied."""
+    want = _frame_shape(rows, cols, batch)
+    if frame.dtype != np.uint8 or frame.shape != want or frame.strides[-1] != 1:
+        raise ValueError("frame of shape %s / dtype %s: uint8 %s expected" % (frame.shape, frame.dtype, want))
+    if frame.ndim == 3 and frame.strides[0] != frame.strides[1] * rows:
+        frame = np.ascontiguousarray(frame)
+    return frame
+
+
 class _DeviceView:
     """A topic buffer of the C session for torch.as_tensor (the CUDA array interface); keeps the session alive."""
 
@@ -858,13 +888,7 @@ class FusionSession:
     def _call(self, which, frame):
         import torch
 
-        want = (self.rows, self.cols) if self.batch == 1 else (self.batch, self.rows, self.cols)
-        if not isinstance(frame, torch.Tensor) or not frame.is_cuda or frame.dtype != torch.uint8:
-            raise ValueError("frame must be a uint8 CUDA tensor")
-        if self.batch == 1 and frame.dim() == 3 and frame.shape[0] == 1:
-            frame = frame[0]
-        if tuple(frame.shape) != want or frame.stride(-1) != 1:
-            raise ValueError("frame of shape %s: %s with unit column stride expected" % (tuple(frame.shape), want))
+        frame = device_frames(frame, self.rows, self.cols, self.batch)
         fstride = frame.stride(0) if frame.dim() == 3 else 0
         stream = torch.cuda.current_stream(frame.device).cuda_stream
         return self._views(self.callback_device(which, frame.data_ptr(), frame.stride(-2), fstride, stream))
@@ -885,11 +909,7 @@ class FusionSession:
     def callback_host(self, which, frame: np.ndarray, capacity=None):
         """d2pc_fusion_node_callback: numpy uint8 frame(s) in, {topic: numpy array} out.  `capacity` = {topic: bytes}
         shrinks the buffers offered for those topics (tests of D2PC_ERR_CAPACITY)."""
-        want = (self.rows, self.cols) if self.batch == 1 else (self.batch, self.rows, self.cols)
-        if frame.dtype != np.uint8 or frame.shape != want or frame.strides[-1] != 1:
-            raise ValueError("frame of shape %s / dtype %s: uint8 %s expected" % (frame.shape, frame.dtype, want))
-        if frame.ndim == 3 and frame.strides[0] != frame.strides[1] * self.rows:
-            frame = np.ascontiguousarray(frame)
+        frame = host_frames(frame, self.rows, self.cols, self.batch)
         io = FusionNodeHostTopics()
         io.struct_size = ctypes.sizeof(FusionNodeHostTopics)
         bufs = []

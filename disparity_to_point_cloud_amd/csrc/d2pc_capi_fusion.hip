@@ -51,67 +51,49 @@ int d2pc_fuse_device(d2pc_ctx *ctx, const d2pc_fuse_desc *desc, void *stream) {
     return fail(ctx, D2PC_ERR_BAD_SIZE, "crop %d/%d/%d/%d does not fit %dx%d", d.crop_left, d.crop_right, d.crop_top,
                 d.crop_bottom, d.width, d.height);
   if (!d.fused) return fail(ctx, D2PC_ERR_INVALID_ARG, "null fused output");
-  const int n_in = d.combined ? 6 : 4;
+  const int n_in = d.combined ? 6 : 4, nf = d.n_frames;
+  Plane in[6];
   for (int p = 0; p < n_in; ++p) {
-    if (!d.planes[p]) return fail(ctx, D2PC_ERR_INVALID_ARG, "input plane %d is null", p);
-    if (d.pitch[p] < size_t(d.width) || d.pitch[p] * size_t(d.height) > 0xffffffffull)  // 32-bit row offsets in the kernel
-      return fail(ctx, D2PC_ERR_BAD_SIZE, "pitch of plane %d smaller than the width (or plane >= 4 GiB)", p);
-    if (d.n_frames > 1 && d.frame_stride[p] < size_t(d.height - 1) * d.pitch[p] + size_t(d.width))
-      return fail(ctx, D2PC_ERR_BAD_SIZE, "frame stride of plane %d too small", p);
+    in[p] = Plane{d.planes[p], d.pitch[p], d.frame_stride[p], size_t(d.width), d.height};
+    if (!in[p].p) return fail(ctx, D2PC_ERR_INVALID_ARG, "input plane %d is null", p);
+    if (!in[p].fits(nf, Bound32::Plane))
+      return fail(ctx, D2PC_ERR_BAD_SIZE, "pitch / frame stride of plane %d too small (or plane >= 4 GiB)", p);
   }
   const int ow = d.width - d.crop_left - d.crop_right, oh = d.height - d.crop_top - d.crop_bottom;
-  // byte extent of a (w x h) x n_frames plane
-  auto extent = [&](size_t pitch, size_t fstride, int w, int h) {
-    return (w <= 0 || h <= 0) ? size_t(0) : size_t(d.n_frames - 1) * fstride + size_t(h - 1) * pitch + size_t(w);
-  };
-  if (ow > 0 && oh > 0) {
-    if (d.fused_pitch < size_t(ow) || d.fused_pitch * size_t(oh) > 0xffffffffull ||
-        (d.n_frames > 1 && d.fused_frame_stride < size_t(oh - 1) * d.fused_pitch + size_t(ow)))
-      return fail(ctx, D2PC_ERR_BAD_SIZE, "fused pitch / frame stride too small");
-  }
-  if (d.combined && (d.combined_pitch < size_t(d.width) || d.combined_pitch * size_t(d.height) > 0xffffffffull ||
-                     (d.n_frames > 1 && d.combined_frame_stride < size_t(d.height - 1) * d.combined_pitch + size_t(d.width))))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "combined pitch / frame stride too small");
-  struct Range { uintptr_t lo, hi; };
-  auto overlaps = [](Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; };
-  const Range rf{reinterpret_cast<uintptr_t>(d.fused),
-                 reinterpret_cast<uintptr_t>(d.fused) + extent(d.fused_pitch, d.fused_frame_stride, ow, oh)};
-  const Range rc{reinterpret_cast<uintptr_t>(d.combined),
-                 reinterpret_cast<uintptr_t>(d.combined) +
-                     (d.combined ? extent(d.combined_pitch, d.combined_frame_stride, d.width, d.height) : 0)};
-  if (d.combined && overlaps(rf, rc)) return fail(ctx, D2PC_ERR_INVALID_ARG, "fused and combined outputs overlap");
-  for (int p = 0; p < n_in; ++p) {
-    const Range ri{reinterpret_cast<uintptr_t>(d.planes[p]),
-                   reinterpret_cast<uintptr_t>(d.planes[p]) + extent(d.pitch[p], d.frame_stride[p], d.width, d.height)};
-    if (overlaps(ri, rf) || (d.combined && overlaps(ri, rc)))
+  const Plane fused{d.fused, d.fused_pitch, d.fused_frame_stride, size_t(ow), oh};  // empty when the crop leaves nothing
+  const Plane combined{d.combined, d.combined_pitch, d.combined_frame_stride, size_t(d.width), d.height};
+  if (!fused.empty() && !fused.fits(nf, Bound32::Plane))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "fused pitch / frame stride too small (or plane >= 4 GiB)");
+  if (combined.p && !combined.fits(nf, Bound32::Plane))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "combined pitch / frame stride too small (or plane >= 4 GiB)");
+  if (overlaps(fused, combined, nf)) return fail(ctx, D2PC_ERR_INVALID_ARG, "fused and combined outputs overlap");
+  for (int p = 0; p < n_in; ++p)
+    if (overlaps(in[p], fused, nf) || overlaps(in[p], combined, nf))
       return fail(ctx, D2PC_ERR_INVALID_ARG, "an output overlaps input plane %d (in-place fusion is not supported)", p);
-  }
-  if (ow <= 0 || oh <= 0) {
-    if (!d.combined) return D2PC_OK;  // nothing to write
-  }
+  if (fused.empty() && !combined.p) return D2PC_OK;  // nothing to write
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   FuseArgs a;
   for (int p = 0; p < 6; ++p) {
-    const int q = p < n_in ? p : 0;  // unused grad planes: any valid pointer
-    a.in[p] = static_cast<const uint8_t *>(d.planes[q]);
-    a.in_pitch[p] = uint32_t(d.pitch[q]);
-    a.in_frame_stride[p] = d.n_frames > 1 ? d.frame_stride[q] : 0;
+    const Plane &q = in[p < n_in ? p : 0];  // unused grad planes: any valid pointer
+    a.in[p] = static_cast<const uint8_t *>(q.p);
+    a.in_pitch[p] = uint32_t(q.pitch);
+    a.in_frame_stride[p] = q.kernel_frame_stride(nf);
   }
   a.fused = static_cast<uint8_t *>(d.fused);
-  a.fused_pitch = uint32_t(d.fused_pitch);
-  a.fused_frame_stride = d.n_frames > 1 ? d.fused_frame_stride : 0;
+  a.fused_pitch = uint32_t(fused.pitch);
+  a.fused_frame_stride = fused.kernel_frame_stride(nf);
   a.combined = static_cast<uint8_t *>(d.combined);
-  a.combined_pitch = uint32_t(d.combined_pitch);
-  a.combined_frame_stride = d.n_frames > 1 ? d.combined_frame_stride : 0;
+  a.combined_pitch = uint32_t(combined.pitch);
+  a.combined_frame_stride = combined.kernel_frame_stride(nf);
   a.width = uint32_t(d.width);
   a.height = uint32_t(d.height);
   a.n_frames = uint32_t(d.n_frames);
   a.rule = d.rule;
   a.crop_left = uint32_t(d.crop_left);
   a.crop_top = uint32_t(d.crop_top);
-  a.out_width = uint32_t(ow > 0 ? ow : 0);
-  a.out_height = uint32_t(oh > 0 ? oh : 0);
+  a.out_width = uint32_t(ow);  // (the crop checks above: neither is negative)
+  a.out_height = uint32_t(oh);
   D2PC_HIP(ctx, launch_fuse(a, static_cast<hipStream_t>(stream), ctx->fuse_rows));
   return D2PC_OK;
 }
@@ -123,15 +105,11 @@ int d2pc_rotate_cw_device(d2pc_ctx *ctx, const void *d_src, int cols, int rows, 
   if (!d_src || !d_dst) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
   if (cols <= 0 || rows <= 0 || n_frames <= 0 || n_frames > 65535)
     return fail(ctx, D2PC_ERR_BAD_SIZE, "bad size %dx%d x%d", cols, rows, n_frames);
-  if (src_pitch < size_t(cols) || dst_pitch < size_t(rows) || src_pitch > 0xffffffffull || dst_pitch > 0xffffffffull)
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "pitch smaller than the row (src rows are %d, dst rows %d pixels)", cols, rows);
-  const size_t src_extent = size_t(rows - 1) * src_pitch + size_t(cols), dst_extent = size_t(cols - 1) * dst_pitch + size_t(rows);
-  if (n_frames > 1 && (src_frame_stride < src_extent || dst_frame_stride < dst_extent))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "frame stride too small");
-  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-  const uintptr_t s1 = s0 + size_t(n_frames - 1) * src_frame_stride + src_extent;
-  const uintptr_t d1 = d0 + size_t(n_frames - 1) * dst_frame_stride + dst_extent;
-  if (s0 < d1 && d0 < s1) return fail(ctx, D2PC_ERR_INVALID_ARG, "source and destination overlap");
+  const Plane src{d_src, src_pitch, src_frame_stride, size_t(cols), rows};
+  const Plane dst{d_dst, dst_pitch, dst_frame_stride, size_t(rows), cols};
+  if (!src.fits(n_frames, Bound32::Pitch) || !dst.fits(n_frames, Bound32::Pitch))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "pitch / frame stride too small (src rows are %d, dst rows %d pixels)", cols, rows);
+  if (overlaps(src, dst, n_frames)) return fail(ctx, D2PC_ERR_INVALID_ARG, "source and destination overlap");
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   RotateArgs a;
@@ -139,8 +117,8 @@ int d2pc_rotate_cw_device(d2pc_ctx *ctx, const void *d_src, int cols, int rows, 
   a.dst = static_cast<uint8_t *>(d_dst);
   a.src_pitch = uint32_t(src_pitch);
   a.dst_pitch = uint32_t(dst_pitch);
-  a.src_frame_stride = n_frames > 1 ? src_frame_stride : 0;
-  a.dst_frame_stride = n_frames > 1 ? dst_frame_stride : 0;
+  a.src_frame_stride = src.kernel_frame_stride(n_frames);
+  a.dst_frame_stride = dst.kernel_frame_stride(n_frames);
   a.cols = uint32_t(cols);
   a.rows = uint32_t(rows);
   a.n_frames = uint32_t(n_frames);
@@ -174,32 +152,19 @@ int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, 
   if (d.n < 11 || d.x < 0 || d.y < 0 || d.x > d.width - d.n || d.y > d.height - d.n)
     return fail(ctx, D2PC_ERR_BAD_SIZE, "square %d,%d,%d: n < 11 or outside %dx%d", d.x, d.y, d.n, d.width, d.height);
   if (!d.src || !d.out) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
-  // byte extent of a (w x h) x n_frames plane; 32-bit row offsets in the kernel
-  auto extent = [&](size_t pitch, size_t fstride, int w, int h) {
-    return size_t(d.n_frames - 1) * fstride + size_t(h - 1) * pitch + size_t(w);
-  };
-  auto bad_plane = [&](size_t pitch, size_t fstride, int w, int h) {
-    return pitch < size_t(w) || pitch * size_t(h) > 0xffffffffull ||
-           (d.n_frames > 1 && fstride < size_t(h - 1) * pitch + size_t(w));
-  };
-  if (bad_plane(d.src_pitch, d.src_frame_stride, d.width, d.height))
+  const int nf = d.n_frames;
+  const Plane src{d.src, d.src_pitch, d.src_frame_stride, size_t(d.width), d.height};
+  const Plane out{d.out, d.out_pitch, d.out_frame_stride, size_t(d.n), d.n};
+  const Plane grad{d.grad, d.grad_pitch, d.grad_frame_stride, size_t(d.n), d.n};
+  if (!src.fits(nf, Bound32::Plane))
     return fail(ctx, D2PC_ERR_BAD_SIZE, "source pitch / frame stride too small (or plane >= 4 GiB)");
-  if (bad_plane(d.out_pitch, d.out_frame_stride, d.n, d.n))
+  if (!out.fits(nf, Bound32::Plane))
     return fail(ctx, D2PC_ERR_BAD_SIZE, "out pitch / frame stride too small (or plane >= 4 GiB)");
-  if (d.grad && bad_plane(d.grad_pitch, d.grad_frame_stride, d.n, d.n))
+  if (grad.p && !grad.fits(nf, Bound32::Plane))
     return fail(ctx, D2PC_ERR_BAD_SIZE, "grad pitch / frame stride too small (or plane >= 4 GiB)");
-  struct Range { uintptr_t lo, hi; };
-  auto overlaps = [](Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; };
-  auto range = [&](const void *p, size_t pitch, size_t fstride, int w, int h) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Range{lo, lo + (p ? extent(pitch, fstride, w, h) : 0)};
-  };
-  const Range rs = range(d.src, d.src_pitch, d.src_frame_stride, d.width, d.height);
-  const Range ro = range(d.out, d.out_pitch, d.out_frame_stride, d.n, d.n);
-  const Range rg = range(d.grad, d.grad_pitch, d.grad_frame_stride, d.n, d.n);
-  if (overlaps(rs, ro) || (d.grad && overlaps(rs, rg)))
+  if (overlaps(src, out, nf) || overlaps(src, grad, nf))
     return fail(ctx, D2PC_ERR_INVALID_ARG, "an output overlaps the source (in-place filtering is not supported)");
-  if (d.grad && overlaps(ro, rg)) return fail(ctx, D2PC_ERR_INVALID_ARG, "out and grad overlap");
+  if (overlaps(out, grad, nf)) return fail(ctx, D2PC_ERR_INVALID_ARG, "out and grad overlap");
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   ScoreArgs a;
@@ -209,9 +174,9 @@ int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, 
   a.src_pitch = uint32_t(d.src_pitch);
   a.out_pitch = uint32_t(d.out_pitch);
   a.grad_pitch = uint32_t(d.grad_pitch);
-  a.src_frame_stride = d.n_frames > 1 ? d.src_frame_stride : 0;
-  a.out_frame_stride = d.n_frames > 1 ? d.out_frame_stride : 0;
-  a.grad_frame_stride = d.n_frames > 1 ? d.grad_frame_stride : 0;
+  a.src_frame_stride = src.kernel_frame_stride(nf);
+  a.out_frame_stride = out.kernel_frame_stride(nf);
+  a.grad_frame_stride = grad.kernel_frame_stride(nf);
   a.width = d.width, a.height = d.height, a.x0 = d.x, a.y0 = d.y, a.n = d.n, a.n_frames = d.n_frames;
   a.direction = d.direction;
   a.form = d.form;
@@ -219,7 +184,6 @@ int d2pc_score_filter_device(d2pc_ctx *ctx, const d2pc_score_filter_desc *desc, 
   D2PC_HIP(ctx, launch_score_filter(a, static_cast<hipStream_t>(stream)));
   return D2PC_OK;
 }
-
 
 // ---------------------------------------------------------------------------
 // colorizeDepth + the view of DisparityCb1/2 (src/depth_map_fusion.cpp:45-61,306-360)
@@ -251,31 +215,16 @@ int d2pc_colorize_device(d2pc_ctx *ctx, const d2pc_colorize_desc *desc, void *st
     return fail(ctx, D2PC_ERR_BAD_SIZE, "view %d,%d %dx%d: empty or outside %dx%d", d.x, d.y, d.w, d.h, fw, fh);
   if (!d.src) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
   if (!d.gray && !d.rgb) return fail(ctx, D2PC_ERR_INVALID_ARG, "neither gray nor rgb output");
-  // a plane of n_frames x (h rows of `row` bytes)
-  auto extent = [&](size_t pitch, size_t fstride, size_t row, int h) {
-    return size_t(d.n_frames - 1) * fstride + size_t(h - 1) * pitch + row;
-  };
-  auto bad_plane = [&](size_t pitch, size_t fstride, size_t row, int h) {
-    return pitch < row || pitch > 0xffffffffull || (d.n_frames > 1 && fstride < size_t(h - 1) * pitch + row);
-  };
-  if (bad_plane(d.src_pitch, d.src_frame_stride, size_t(d.cols), d.rows))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "source pitch / frame stride too small");
-  if (d.gray && bad_plane(d.gray_pitch, d.gray_frame_stride, size_t(d.w), d.h))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "gray pitch / frame stride too small");
-  if (d.rgb && bad_plane(d.rgb_pitch, d.rgb_frame_stride, 3 * size_t(d.w), d.h))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "rgb pitch (< 3 w) / frame stride too small");
-  struct Range { uintptr_t lo, hi; };
-  auto overlaps = [](Range a, Range b) { return a.lo < b.hi && b.lo < a.hi; };
-  auto range = [&](const void *p, size_t pitch, size_t fstride, size_t row, int h) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return Range{lo, lo + (p ? extent(pitch, fstride, row, h) : 0)};
-  };
-  const Range rs = range(d.src, d.src_pitch, d.src_frame_stride, size_t(d.cols), d.rows);
-  const Range rg = range(d.gray, d.gray_pitch, d.gray_frame_stride, size_t(d.w), d.h);
-  const Range rc = range(d.rgb, d.rgb_pitch, d.rgb_frame_stride, 3 * size_t(d.w), d.h);
-  if ((d.gray && overlaps(rs, rg)) || (d.rgb && overlaps(rs, rc)))
+  const int nf = d.n_frames;
+  const Plane src{d.src, d.src_pitch, d.src_frame_stride, size_t(d.cols), d.rows};
+  const Plane gray{d.gray, d.gray_pitch, d.gray_frame_stride, size_t(d.w), d.h};
+  const Plane rgb{d.rgb, d.rgb_pitch, d.rgb_frame_stride, 3 * size_t(d.w), d.h};
+  if (!src.fits(nf, Bound32::Pitch)) return fail(ctx, D2PC_ERR_BAD_SIZE, "source pitch / frame stride too small");
+  if (gray.p && !gray.fits(nf, Bound32::Pitch)) return fail(ctx, D2PC_ERR_BAD_SIZE, "gray pitch / frame stride too small");
+  if (rgb.p && !rgb.fits(nf, Bound32::Pitch)) return fail(ctx, D2PC_ERR_BAD_SIZE, "rgb pitch (< 3 w) / frame stride too small");
+  if (overlaps(src, gray, nf) || overlaps(src, rgb, nf))
     return fail(ctx, D2PC_ERR_INVALID_ARG, "an output overlaps the source");
-  if (d.gray && d.rgb && overlaps(rg, rc)) return fail(ctx, D2PC_ERR_INVALID_ARG, "gray and rgb overlap");
+  if (overlaps(gray, rgb, nf)) return fail(ctx, D2PC_ERR_INVALID_ARG, "gray and rgb overlap");
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   ColorizeArgs a;
@@ -283,9 +232,9 @@ int d2pc_colorize_device(d2pc_ctx *ctx, const d2pc_colorize_desc *desc, void *st
   a.gray = static_cast<uint8_t *>(d.gray);
   a.rgb = static_cast<uint8_t *>(d.rgb);
   a.src_pitch = d.src_pitch, a.gray_pitch = d.gray_pitch, a.rgb_pitch = d.rgb_pitch;
-  a.src_frame_stride = d.n_frames > 1 ? d.src_frame_stride : 0;
-  a.gray_frame_stride = d.n_frames > 1 ? d.gray_frame_stride : 0;
-  a.rgb_frame_stride = d.n_frames > 1 ? d.rgb_frame_stride : 0;
+  a.src_frame_stride = src.kernel_frame_stride(nf);
+  a.gray_frame_stride = gray.kernel_frame_stride(nf);
+  a.rgb_frame_stride = rgb.kernel_frame_stride(nf);
   a.cols = d.cols, a.rows = d.rows, a.x = d.x, a.y = d.y, a.w = d.w, a.h = d.h;
   a.n_frames = d.n_frames, a.rotate_cw = d.rotate_cw;
   D2PC_HIP(ctx, launch_colorize(a, static_cast<hipStream_t>(stream)));

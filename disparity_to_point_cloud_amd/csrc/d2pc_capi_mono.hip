@@ -32,17 +32,12 @@ int d2pc_mono16_to_mono8_device(d2pc_ctx *ctx, const void *d_src, int width, int
   if (!d_src || !d_dst) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
   if (width <= 0 || height <= 0 || n_frames <= 0 || n_frames > 65535)
     return fail(ctx, D2PC_ERR_BAD_SIZE, "bad size %dx%d x%d", width, height, n_frames);
-  if (src_row_stride < size_t(width) * 2 || src_row_stride % 2 != 0 || dst_row_stride < size_t(width) ||
-      src_row_stride > 0xffffffffull || dst_row_stride > 0xffffffffull || reinterpret_cast<uintptr_t>(d_src) % 2 != 0)
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "bad row stride or alignment (source rows hold %d uint16 samples)", width);
-  const size_t src_extent = size_t(height - 1) * src_row_stride + size_t(width) * 2;
-  const size_t dst_extent = size_t(height - 1) * dst_row_stride + size_t(width);
-  if (n_frames > 1 && (src_frame_stride < src_extent || src_frame_stride % 2 != 0 || dst_frame_stride < dst_extent))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "frame stride too small");
-  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src), d0 = reinterpret_cast<uintptr_t>(d_dst);
-  const uintptr_t s1 = s0 + size_t(n_frames - 1) * src_frame_stride + src_extent;
-  const uintptr_t d1 = d0 + size_t(n_frames - 1) * dst_frame_stride + dst_extent;
-  if (s0 < d1 && d0 < s1) return fail(ctx, D2PC_ERR_INVALID_ARG, "source and destination overlap");
+  const Plane src{d_src, src_row_stride, src_frame_stride, size_t(width) * 2, height};  // rows of uint16 samples
+  const Plane dst{d_dst, dst_row_stride, dst_frame_stride, size_t(width), height};
+  if (!src.fits(n_frames, Bound32::Pitch) || !dst.fits(n_frames, Bound32::Pitch) || src_row_stride % 2 != 0 ||
+      reinterpret_cast<uintptr_t>(d_src) % 2 != 0 || (n_frames > 1 && src_frame_stride % 2 != 0))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "bad row / frame stride or alignment (source rows hold %d uint16 samples)", width);
+  if (overlaps(src, dst, n_frames)) return fail(ctx, D2PC_ERR_INVALID_ARG, "source and destination overlap");
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   MedianArgs m;
@@ -52,8 +47,8 @@ int d2pc_mono16_to_mono8_device(d2pc_ctx *ctx, const void *d_src, int width, int
   m.n_frames = uint32_t(n_frames);
   m.src_row_stride = uint32_t(src_row_stride);
   m.dst_row_stride = uint32_t(dst_row_stride);
-  m.src_frame_stride = n_frames > 1 ? src_frame_stride : 0;
-  m.dst_frame_stride = n_frames > 1 ? dst_frame_stride : 0;
+  m.src_frame_stride = src.kernel_frame_stride(n_frames);
+  m.dst_frame_stride = dst.kernel_frame_stride(n_frames);
   D2PC_HIP(ctx, launch_mono16_to_mono8(d_src, d_dst, m, static_cast<hipStream_t>(stream)));
   return D2PC_OK;
 }
@@ -66,11 +61,10 @@ static int median_device(d2pc_ctx *ctx, const void *d_src, int width, int height
   if (!median_ksize_supported(ksize)) return fail(ctx, D2PC_ERR_INVALID_ARG, "ksize %d not in {3,5,7,9,11}", ksize);
   if (width <= 0 || height <= 0 || n_frames <= 0 || n_frames > 65535)
     return fail(ctx, D2PC_ERR_BAD_SIZE, "bad size %dx%d x%d", width, height, n_frames);
-  if (src_row_stride < size_t(width) || dst_row_stride < size_t(width) || src_row_stride > 0xffffffffull ||
-      dst_row_stride > 0xffffffffull)
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "row stride smaller than the width");
-  if (n_frames > 1 && (src_frame_stride < size_t(height) * src_row_stride || dst_frame_stride < size_t(height) * dst_row_stride))
-    return fail(ctx, D2PC_ERR_BAD_SIZE, "frame stride too small");
+  const Plane src{d_src, src_row_stride, src_frame_stride, size_t(width), height};
+  const Plane dst{d_dst, dst_row_stride, dst_frame_stride, size_t(width), height};
+  if (!src.fits(n_frames, Bound32::Pitch, FrameRule::WholeRows) || !dst.fits(n_frames, Bound32::Pitch, FrameRule::WholeRows))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "row stride smaller than the width, or frame stride smaller than a frame's rows");
   DeviceGuard guard(ctx->device);
   if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
   MedianArgs m;

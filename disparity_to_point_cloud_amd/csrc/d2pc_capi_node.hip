@@ -81,6 +81,12 @@ uint32_t publishes(const d2pc_fusion_node *n, int which) {
   }
 }
 
+// one of the node's own planes: w x h pixels of `ch` bytes, rows and frames packed
+Plane tight(const void *p, int w, int h, int ch = 1) {
+  const size_t row = size_t(w) * size_t(ch);
+  return Plane{p, row, row * size_t(h), row, h};
+}
+
 void describe(const d2pc_fusion_node *n, int id, d2pc_fusion_node_topic *t) {
   const int sq = n->geo.n, fw = n->geo.fused_width, fh = n->geo.fused_height;
   void *data = nullptr;
@@ -94,51 +100,53 @@ void describe(const d2pc_fusion_node *n, int id, d2pc_fusion_node_topic *t) {
     case D2PC_TOPIC_FUSED_DEPTH_MAP: data = n->fused, w = fw, h = fh; break;
     default: data = n->gradient, w = fw, h = fh, ch = 3; break;
   }
-  t->data = data;
-  t->pitch = size_t(w) * size_t(ch);
-  t->frame_stride = t->pitch * size_t(h);
+  const Plane pl = tight(data, w, h, ch);
+  t->data = data, t->pitch = pl.pitch, t->frame_stride = pl.frame_stride;
   t->width = w, t->height = h, t->channels = ch, t->reserved = 0;
 }
 
-int colorize(d2pc_fusion_node *n, const void *src, int cols, int rows, size_t pitch, size_t fstride, int rotate, int x,
-             int y, int w, int h, uint8_t *gray, uint8_t *rgb, void *stream) {
+// the view (x, y, w, h) of `src` (8-bit frames of src.row_bytes x src.rows pixels), rotated first or not, into tight planes
+int colorize(d2pc_fusion_node *n, const Plane &src, int rotate, int x, int y, int w, int h, uint8_t *gray, uint8_t *rgb,
+             void *stream) {
   d2pc_colorize_desc d;
   d2pc_colorize_desc_init(&d);
-  d.rotate_cw = rotate, d.cols = cols, d.rows = rows, d.n_frames = n->cfg.batch;
+  d.rotate_cw = rotate, d.cols = int(src.row_bytes), d.rows = src.rows, d.n_frames = n->cfg.batch;
   d.x = x, d.y = y, d.w = w, d.h = h;
-  d.src = src, d.src_pitch = pitch, d.src_frame_stride = fstride;
-  d.gray = gray, d.gray_pitch = size_t(w), d.gray_frame_stride = size_t(w) * size_t(h);
-  d.rgb = rgb, d.rgb_pitch = 3 * size_t(w), d.rgb_frame_stride = 3 * size_t(w) * size_t(h);
+  const Plane g = tight(gray, w, h), c = tight(rgb, w, h, 3);
+  d.src = src.p, d.src_pitch = src.pitch, d.src_frame_stride = src.frame_stride;
+  d.gray = gray, d.gray_pitch = g.pitch, d.gray_frame_stride = g.frame_stride;
+  d.rgb = rgb, d.rgb_pitch = c.pitch, d.rgb_frame_stride = c.frame_stride;
   return d2pc_colorize_device(n->ctx, &d, stream);
 }
 
-int score_filter(d2pc_fusion_node *n, const void *src, int width, int height, size_t pitch, size_t fstride, int x, int y,
-                 int direction, uint8_t *out, void *stream) {
+int score_filter(d2pc_fusion_node *n, const Plane &src, int x, int y, int direction, uint8_t *out, void *stream) {
   d2pc_score_filter_desc d;
   d2pc_score_filter_desc_init(&d);
-  d.direction = direction, d.form = n->cfg.score_form, d.width = width, d.height = height, d.n_frames = n->cfg.batch;
+  d.direction = direction, d.form = n->cfg.score_form, d.width = int(src.row_bytes), d.height = src.rows, d.n_frames = n->cfg.batch;
   d.x = x, d.y = y, d.n = n->geo.n;
-  d.src = src, d.src_pitch = pitch, d.src_frame_stride = fstride;
-  d.out = out, d.out_pitch = size_t(n->geo.n), d.out_frame_stride = size_t(n->geo.n) * size_t(n->geo.n);
+  const Plane o = tight(out, d.n, d.n);
+  d.src = src.p, d.src_pitch = src.pitch, d.src_frame_stride = src.frame_stride;
+  d.out = out, d.out_pitch = o.pitch, d.out_frame_stride = o.frame_stride;
   return d2pc_score_filter_device(n->ctx, &d, stream);
 }
 
 // publishFusedDepthMap (:102-135) behind camera 2's view: either inside the single launch or as two more launches
-int disparity_2(d2pc_fusion_node *n, const void *frame, size_t pitch, size_t fstride, bool fuse, void *stream) {
+int disparity_2(d2pc_fusion_node *n, const Plane &frame, bool fuse, void *stream) {
   const d2pc_fusion_node_config &c = n->cfg;
   const d2pc_fusion_node_geometry_t &g = n->geo;
-  const size_t sq = size_t(g.n), plane = sq * sq, fw = size_t(g.fused_width), fh = size_t(g.fused_height);
+  const Plane sq = tight(nullptr, g.n, g.n), sq3 = tight(nullptr, g.n, g.n, 3);
+  const Plane fu = tight(n->fused, g.fused_width, g.fused_height), fu3 = tight(nullptr, g.fused_width, g.fused_height, 3);
   if (fuse && c.single_launch && c.rule == D2PC_FUSE_GRAD_FILTER) {
     DeviceGuard guard(n->ctx->device);
     if (!guard.ok) return fail(n->ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", n->ctx->device);
     NodeFuseArgs a;
-    a.frame2 = static_cast<const uint8_t *>(frame), a.frame2_pitch = pitch, a.frame2_frame_stride = c.batch > 1 ? fstride : 0;
+    a.frame2 = static_cast<const uint8_t *>(frame.p), a.frame2_pitch = frame.pitch, a.frame2_frame_stride = frame.frame_stride;
     a.depth1 = n->depth[0], a.score1 = n->score1, a.score2 = n->score2, a.spare = n->spare;
-    a.depth1_pitch = a.score1_pitch = a.score2_pitch = a.spare_pitch = sq;
-    a.depth1_frame_stride = a.score1_frame_stride = a.score2_frame_stride = a.spare_frame_stride = plane;
-    a.rgb2 = n->color[1], a.rgb2_pitch = 3 * sq, a.rgb2_frame_stride = 3 * plane;
-    a.fused = n->fused, a.fused_pitch = fw, a.fused_frame_stride = fw * fh;
-    a.gradient = n->gradient, a.gradient_pitch = 3 * fw, a.gradient_frame_stride = 3 * fw * fh;
+    a.depth1_pitch = a.score1_pitch = a.score2_pitch = a.spare_pitch = sq.pitch;
+    a.depth1_frame_stride = a.score1_frame_stride = a.score2_frame_stride = a.spare_frame_stride = sq.frame_stride;
+    a.rgb2 = n->color[1], a.rgb2_pitch = sq3.pitch, a.rgb2_frame_stride = sq3.frame_stride;
+    a.fused = n->fused, a.fused_pitch = fu.pitch, a.fused_frame_stride = fu.frame_stride;
+    a.gradient = n->gradient, a.gradient_pitch = fu3.pitch, a.gradient_frame_stride = fu3.frame_stride;
     a.table = n->table;
     a.rows = c.rows, a.x2 = g.x2, a.y2 = g.y2, a.n = g.n;
     a.crop_left = c.crop_left, a.crop_top = c.crop_top, a.out_width = g.fused_width, a.out_height = g.fused_height;
@@ -146,19 +154,18 @@ int disparity_2(d2pc_fusion_node *n, const void *frame, size_t pitch, size_t fst
     D2PC_HIP(n->ctx, launch_node_fuse(a, static_cast<hipStream_t>(stream)));
     return D2PC_OK;
   }
-  int st = colorize(n, frame, c.cols, c.rows, pitch, fstride, 1, g.x2, g.y2, g.n, g.n, n->depth[1], n->color[1], stream);
+  int st = colorize(n, frame, 1, g.x2, g.y2, g.n, g.n, n->depth[1], n->color[1], stream);
   if (st != D2PC_OK || !fuse) return st;
   d2pc_fuse_desc d;
   d2pc_fuse_desc_init(&d);
   d.rule = c.rule, d.width = d.height = g.n, d.n_frames = c.batch;
   d.crop_left = c.crop_left, d.crop_right = c.crop_right, d.crop_top = c.crop_top, d.crop_bottom = c.crop_bottom;
   const uint8_t *in[6] = {n->depth[0], n->depth[1], n->score1, n->score2, n->score1, n->score2};  // score and grad: one plane (:77,:96)
-  for (int p = 0; p < 6; ++p) d.planes[p] = in[p], d.pitch[p] = sq, d.frame_stride[p] = plane;
-  d.fused = n->fused, d.fused_pitch = fw, d.fused_frame_stride = fw * fh;
-  d.combined = n->spare, d.combined_pitch = sq, d.combined_frame_stride = plane;
+  for (int p = 0; p < 6; ++p) d.planes[p] = in[p], d.pitch[p] = sq.pitch, d.frame_stride[p] = sq.frame_stride;
+  d.fused = n->fused, d.fused_pitch = fu.pitch, d.fused_frame_stride = fu.frame_stride;
+  d.combined = n->spare, d.combined_pitch = sq.pitch, d.combined_frame_stride = sq.frame_stride;
   if ((st = d2pc_fuse_device(n->ctx, &d, stream)) != D2PC_OK) return st;
-  return colorize(n, n->fused, g.fused_width, g.fused_height, fw, fw * fh, 0, 0, 0, g.fused_width, g.fused_height, nullptr,
-                  n->gradient, stream);
+  return colorize(n, fu, 0, 0, 0, g.fused_width, g.fused_height, nullptr, n->gradient, stream);
 }
 
 }  // namespace
@@ -242,28 +249,29 @@ int d2pc_fusion_node_callback_device(d2pc_fusion_node *node, int which, const vo
     return fail(ctx, D2PC_ERR_INVALID_ARG, "null frame or bad d2pc_fusion_node_topics");
   const d2pc_fusion_node_config &c = node->cfg;
   const d2pc_fusion_node_geometry_t &g = node->geo;
-  if (pitch < size_t(c.cols) || pitch > 0xffffffffull ||
-      (c.batch > 1 && frame_stride < size_t(c.rows - 1) * pitch + size_t(c.cols)))
+  Plane frame{d_frame, pitch, frame_stride, size_t(c.cols), c.rows};
+  if (!frame.fits(c.batch, Bound32::Pitch))
     return fail(ctx, D2PC_ERR_BAD_SIZE, "frame pitch / frame stride too small for %dx%d", c.cols, c.rows);
-  const size_t fstride = c.batch > 1 ? frame_stride : 0;
+  frame.frame_stride = frame.kernel_frame_stride(c.batch);
   const uint32_t mask = publishes(node, which);
   int st = D2PC_OK;
   switch (which) {
     case D2PC_NODE_DISPARITY_1:
-      st = colorize(node, d_frame, c.cols, c.rows, pitch, fstride, 0, g.x1, g.y1, g.n, g.n, node->depth[0], node->color[0], stream);
+      st = colorize(node, frame, 0, g.x1, g.y1, g.n, g.n, node->depth[0], node->color[0], stream);
       break;
     case D2PC_NODE_MATCHING_SCORE_1:
-      st = score_filter(node, d_frame, c.cols, c.rows, pitch, fstride, g.x1, g.y1, 0, node->score1, stream);
+      st = score_filter(node, frame, g.x1, g.y1, 0, node->score1, stream);
       break;
     case D2PC_NODE_MATCHING_SCORE_2: {
-      const size_t rp = size_t(c.rows), rf = size_t(c.rows) * size_t(c.cols);
-      st = d2pc_rotate_cw_device(ctx, d_frame, c.cols, c.rows, pitch, fstride, c.batch, node->rot, rp, rf, stream);
-      if (st == D2PC_OK) st = score_filter(node, node->rot, c.rows, c.cols, rp, rf, g.x2, g.y2, 1, node->score2, stream);
+      const Plane rot = tight(node->rot, c.rows, c.cols);
+      st = d2pc_rotate_cw_device(ctx, d_frame, c.cols, c.rows, pitch, frame.frame_stride, c.batch, node->rot, rot.pitch,
+                                 rot.frame_stride, stream);
+      if (st == D2PC_OK) st = score_filter(node, rot, g.x2, g.y2, 1, node->score2, stream);
       break;
     }
     default: {
       const bool fuse = (mask >> D2PC_TOPIC_FUSED_DEPTH_MAP) & 1u;
-      st = disparity_2(node, d_frame, pitch, fstride, fuse, stream);
+      st = disparity_2(node, frame, fuse, stream);
       // cropped_score_combined_ IS cropped_score_1_ (:113): from now on camera 1's score / grad plane is the combined one
       if (st == D2PC_OK && fuse) std::swap(node->score1, node->spare);
       break;

@@ -9,6 +9,13 @@
 //   d2pc_capi_fusion.hip   depth-map fusion inner loop, rotate, crop
 //   d2pc_capi_node.hip     the depth_map_fusion node as a session (d2pc_fusion_node_*)
 //   d2pc_capi_ext.hip      include/d2pc_ext.h: tuning keys, test hooks, device calibration kernels
+//   d2pc_plane.hpp         one image plane (pointer, pitch, frame stride, rows x row bytes): fit, extent, overlap; no HIP.
+//                          Which rule each image entry point passes to Plane::fits (d2pc_process* have make_geom's own):
+//     d2pc_fuse_device, d2pc_score_filter_device         Bound32::Plane (pitch * rows < 2^32), FrameRule::LastRow
+//     d2pc_colorize_device, d2pc_rotate_cw_device        Bound32::Pitch (pitch < 2^32),        FrameRule::LastRow
+//     d2pc_mono16_to_mono8_device                        Bound32::Pitch, FrameRule::LastRow; pitch, frame stride, base even
+//     d2pc_median_device, d2pc_median_roi_device         Bound32::Pitch, FrameRule::WholeRows (rows * pitch); no overlap test
+//     d2pc_fusion_node_callback_device (incoming frame)  Bound32::Pitch, FrameRule::LastRow
 // Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +33,7 @@
 #include "../../include/d2pc_ext.h"
 #include "d2pc_device.hpp"
 #include "d2pc_launch.hpp"
+#include "d2pc_plane.hpp"
 
 using namespace d2pc;  // (host translation units of the library only)
 

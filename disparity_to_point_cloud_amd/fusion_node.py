@@ -66,16 +66,7 @@ class FusionNode:
 
     # -- helpers -------------------------------------------------------------------------------------------------
     def _frame(self, frame):
-        want = (self.rows, self.cols) if self.batch == 1 else (self.batch, self.rows, self.cols)
-        if not isinstance(frame, torch.Tensor) or not frame.is_cuda:
-            raise ValueError("frame must be a CUDA tensor")
-        if frame.dtype != torch.uint8:
-            raise ValueError("frame dtype %s: uint8 (mono8) expected" % frame.dtype)
-        if self.batch == 1 and frame.dim() == 3 and frame.shape[0] == 1:
-            frame = frame[0]
-        if tuple(frame.shape) != want or frame.stride(-1) != 1:
-            raise ValueError("frame of shape %s: %s with unit column stride expected" % (tuple(frame.shape), want))
-        return frame
+        return capi.device_frames(frame, self.rows, self.cols, self.batch)
 
     def _out(self, t):
         return t[0] if self.batch == 1 else t

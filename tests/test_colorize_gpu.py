@@ -204,6 +204,15 @@ def test_misuse_returns_codes_without_launching(ctx):
         ("gray on src", lambda d: setattr(d, "gray", src.data_ptr() + 100), INV),
         ("rgb on src", lambda d: setattr(d, "rgb", src.data_ptr()), INV),
         ("rgb on gray", lambda d: setattr(d, "rgb", gray.data_ptr() + vw), INV),
+        # two faults at once: the order of the checks decides the code -- sizes and the view, then the pointers, then the
+        # planes (source, gray, rgb), then the overlaps
+        ("cols + null src", lambda d: (setattr(d, "cols", 0), setattr(d, "src", None)), SIZE),
+        ("outside x + no output", lambda d: (setattr(d, "x", w - vw + 1), both_null(d)), SIZE),
+        ("src pitch + null src", lambda d: (setattr(d, "src_pitch", w - 1), setattr(d, "src", None)), INV),
+        ("gray pitch + rgb on src", lambda d: (setattr(d, "gray_pitch", vw - 1), setattr(d, "rgb", src.data_ptr())), SIZE),
+        ("rgb frame stride + gray on src",
+         lambda d: (setattr(d, "rgb_frame_stride", 3 * vw * vh - 1), setattr(d, "gray", src.data_ptr() + 100)), SIZE),
+        ("src pitch >= 2^32", lambda d: setattr(d, "src_pitch", 1 << 32), SIZE),
     ]
     for name, mutate, code in cases:
         d = good()

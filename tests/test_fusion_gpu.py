@@ -173,10 +173,19 @@ def test_rejects_bad_arguments():
                             (dict(crop_left=65), 3), (dict(crop_top=60, crop_bottom=5), 3), (dict(fused=None), 1),
                             (dict(fused_pitch=63), 3), (dict(combined_pitch=10), 3), (dict(struct_size=8), 1),
                             (dict(fused=x[2].data_ptr()), 1), (dict(combined=x[0].data_ptr()), 1),
-                            (dict(combined=out.data_ptr()), 1)):
+                            (dict(combined=out.data_ptr()), 1),
+                            # two faults at once: the order of the checks decides the code -- rule, size, crop, the fused
+                            # pointer, the input planes, the fused and combined planes, then the overlaps
+                            (dict(rule=9, width=0), 1), (dict(width=0, fused=None), 3), (dict(fused=None, fused_pitch=63), 1),
+                            (dict(fused_pitch=63, combined=out.data_ptr()), 3),
+                            (dict(combined_pitch=10, fused=x[2].data_ptr()), 3),
+                            # nothing left of the cropped map and no combined plane: the checks still run (an empty plane
+                            # lies inside input 0), except the fused plane's own fit
+                            (dict(crop_left=64, combined=None, fused=x[0].data_ptr() + 1), 1)):
             with pytest.raises(d2pc.D2pcError) as e:
                 ctx.fuse_device(desc(**bad))
             assert e.value.status == status, bad
+        ctx.fuse_device(desc(crop_left=64, combined=None, fused_pitch=0))  # ... and then there is nothing to do
         d = desc()
         d.planes[1] = None
         with pytest.raises(d2pc.D2pcError):
@@ -185,6 +194,18 @@ def test_rejects_bad_arguments():
         d.pitch[3] = 10
         with pytest.raises(d2pc.D2pcError):
             ctx.fuse_device(d)
+        for null, short, status in ((4, 3, 3), (1, 3, 1), (1, 0, 3)):  # the planes are checked one after the other
+            d = desc()
+            d.planes[null], d.pitch[short] = None, 10
+            with pytest.raises(d2pc.D2pcError) as e:
+                ctx.fuse_device(d)
+            assert e.value.status == status, (null, short)
+        # d2pc_rotate_cw_device: pointers, then sizes, then pitches and frame strides, then the overlap
+        lib, s, o = d2pc.load_library(), x[0].data_ptr(), out.data_ptr()
+        for args, status in (((None, 0, 64, 64, 0, 1, o, 64, 0), 1), ((s, 0, 64, 63, 0, 1, o, 64, 0), 3),
+                             ((s, 64, 64, 63, 0, 1, s, 64, 0), 3), ((s, 64, 32, 64, 2047, 2, s, 32, 2048), 3),
+                             ((s, 64, 64, 1 << 32, 0, 1, o, 64, 0), 3), ((s, 64, 64, 64, 0, 1, s + 4095, 64, 0), 1)):
+            assert lib.d2pc_rotate_cw_device(ctx._h, *args, None) == status, args
         torch.cuda.synchronize()
 
 

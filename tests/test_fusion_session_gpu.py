@@ -374,6 +374,14 @@ def test_refusals_leave_the_node_alive(ctx):
     assert call(s._h, 0, None, 188, 0, ctypes.byref(out), None) == 1              # null frame
     assert call(s._h, 0, ok.data_ptr(), 188, 0, None, None) == 1                  # null topics
     assert call(s._h, 0, ok.data_ptr(), 187, 0, ctypes.byref(out), None) == 3     # pitch < cols
+    assert call(s._h, 0, ok.data_ptr(), 1 << 32, 0, ctypes.byref(out), None) == 3  # pitch >= 2^32
+    assert call(s._h, 4, ok.data_ptr(), 187, 0, ctypes.byref(out), None) == 1     # two faults: `which` comes first,
+    assert call(s._h, 0, None, 187, 0, ctypes.byref(out), None) == 1              # ... and so does the null frame
+    with d2pc.FusionSession(ctx, 188, 120, -2, 4, batch=2) as s2:                 # a batch: the frame stride counts
+        two = torch.zeros((2, 120, 188), dtype=torch.uint8, device="cuda")
+        assert call(s2._h, 0, two.data_ptr(), 188, 119 * 188 + 187, ctypes.byref(out), None) == 3
+        assert call(s2._h, 4, two.data_ptr(), 188, 119 * 188 + 187, ctypes.byref(out), None) == 1
+        assert call(s2._h, 0, two.data_ptr(), 188, 119 * 188 + 188, ctypes.byref(out), None) == 0
     out.struct_size = 8
     assert call(s._h, 0, ok.data_ptr(), 188, 0, ctypes.byref(out), None) == 1
     junk = (ctypes.c_uint8 * 512)()                                               # not a node

@@ -139,6 +139,17 @@ def test_median_rejects_bad_arguments():
             ctx.median_device(x.data_ptr(), 8, 8, 8, 64, 1, x.data_ptr(), 8, 64, 3)  # in place
         with pytest.raises(d2pc.D2pcError):
             ctx.median_device(x.data_ptr(), 8, 8, 4, 64, 1, y.data_ptr(), 8, 64, 3)  # stride < width
+        # the codes, and with two faults at once their order: pointers, ksize, sizes, row strides, frame strides
+        lib, s, d = d2pc.load_library(), x.data_ptr(), y.data_ptr()
+        for fn in (lib.d2pc_median_device, lib.d2pc_median_roi_device):
+            for args, status in (((s, 8, 8, 4, 64, 1, s, 8, 64, 3), 1), ((s, 0, 8, 8, 64, 1, d, 8, 64, 4), 1),
+                                 ((s, 0, 8, 4, 64, 1, d, 8, 64, 3), 3), ((s, 8, 8, 1 << 32, 64, 1, d, 8, 64, 3), 3),
+                                 # two frames of 6 x 4 on a pitch of 8: a frame is its whole rows (4 * 8 bytes) here, not
+                                 # the 3 * 8 + 6 bytes up to its last pixel
+                                 ((s, 6, 4, 8, 30, 2, d, 8, 32, 3), 3), ((s, 6, 4, 8, 32, 2, d, 8, 31, 3), 3),
+                                 ((s, 6, 4, 8, 32, 2, d, 8, 32, 3), 0)):
+                assert fn(ctx._h, *args, None) == status, args
+        torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("mode", [d2pc.MODE_PARITY, d2pc.MODE_COMPACT])
@@ -186,6 +197,24 @@ def test_mono16_to_mono8_device_matches_oracle(w, h):
             ctx.mono16_to_mono8_device(src.data_ptr(), w, h, 2 * w - 1 if w > 1 else 1, 0, 1, dst.data_ptr(), w + 3, 0)
         with pytest.raises(d2pc.D2pcError):
             ctx.mono16_to_mono8_device(src.data_ptr(), w, h, 2 * w, 0, 1, src.data_ptr(), w, 0)
+
+
+def test_mono16_to_mono8_device_refusal_codes_and_their_order():
+    """Pointers, then sizes, then row strides / frame strides / alignment, then the overlap: one call each, none launches."""
+    src = torch.zeros((2, 8, 8), dtype=torch.int16, device="cuda")
+    dst = torch.full((2, 8, 8), 7, dtype=torch.uint8, device="cuda")
+    s, d = src.data_ptr(), dst.data_ptr()
+    with d2pc.Context(q=d2pc.make_q()) as ctx:
+        call = d2pc.load_library().d2pc_mono16_to_mono8_device
+        for args, status in (((None, 0, 8, 16, 128, 2, d, 8, 64), 1), ((s, 0, 8, 15, 128, 2, d, 8, 64), 3),
+                             ((s, 8, 8, 15, 128, 2, s, 8, 64), 3), ((s, 8, 8, 14, 128, 2, d, 8, 64), 3),
+                             ((s, 8, 8, 16, 127, 2, s, 8, 64), 3), ((s, 8, 8, 16, 129, 2, d, 8, 64), 3),
+                             ((s, 8, 8, 16, 128, 2, d, 8, 63), 3), ((s + 1, 8, 8, 16, 128, 2, s, 8, 64), 3),
+                             ((s, 8, 8, 1 << 32, 128, 1, d, 8, 64), 3), ((s, 8, 8, 16, 128, 2, s + 255, 8, 64), 1),
+                             ((s, 8, 8, 16, 7, 1, d, 8, 7), 0)):  # one frame: the frame strides do not count
+            assert call(ctx._h, *args, None) == status, args
+        torch.cuda.synchronize()
+    assert (dst[1] == 7).all() and (dst[0] == 0).all()  # only the last call ran, on one frame
 
 
 def test_mono16_to_mono8_device_on_degenerate_shapes():

@@ -149,6 +149,14 @@ def test_misuse_returns_codes_without_launching(ctx):
         ("in place", lambda d: setattr(d, "out", src.data_ptr() + 100), INV),
         ("grad on src", lambda d: setattr(d, "grad", src.data_ptr()), INV),
         ("grad on out", lambda d: setattr(d, "grad", out.data_ptr() + n), INV),
+        # two faults at once: the order of the checks decides the code -- direction and form, the sizes and the square,
+        # then the pointers, then the planes (source, out, grad), then the overlaps
+        ("direction + frames", lambda d: (setattr(d, "direction", 2), setattr(d, "n_frames", 0)), INV),
+        ("n<11 + null src", lambda d: (setattr(d, "n", 10), setattr(d, "src", None)), SIZE),
+        ("src pitch + null out", lambda d: (setattr(d, "src_pitch", w - 1), setattr(d, "out", None)), INV),
+        ("out pitch + in place", lambda d: (setattr(d, "out_pitch", n - 1), setattr(d, "out", src.data_ptr() + 100)), SIZE),
+        ("grad frame stride + grad on src",
+         lambda d: (setattr(d, "grad_frame_stride", n * n - 1), setattr(d, "grad", src.data_ptr())), SIZE),
     ]
     for name, mutate, code in cases:
         d = good()

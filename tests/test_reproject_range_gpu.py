@@ -12,7 +12,7 @@ import disparity_patterns as dp
 import disparity_to_point_cloud_amd as d2pc
 import exact_reproject as ex
 import oracle
-from helpers import line_bits, variant_for
+from helpers import check_compact_is_filtered_parity, line_bits, run_batch, variant_for
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -64,25 +64,6 @@ def host_frames(p):
     """The pattern's frames as the host path gets them: rows on the shape's padded stride."""
     pitch = dp.SHAPES[p.shape][3]
     return [dp.pitched(f, pitch) for f in p.frames]
-
-
-def run_batch(ctx, frames, want_index=True, scale=1.0):
-    """All frames in one launch of d2pc_process_device -> (points (n, stride, 4), index (n, stride) or None, counts)."""
-    from disparity_to_point_cloud_amd.torch_api import DeviceBatch
-    n, (h, w) = len(frames), frames[0].shape
-    tdt = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16}[frames[0].dtype]
-    b = DeviceBatch(ctx, n, h, w, dtype=tdt, want_index=want_index)
-    stack = np.stack(frames)
-    b.disp.copy_(torch.from_numpy(stack.view(np.int16)).view(tdt) if stack.dtype == np.uint16 else torch.from_numpy(stack))
-    b.points.fill_(float("nan"))
-    b.counts.fill_(-7)
-    b.launch(scale=scale)
-    torch.cuda.synchronize()
-    ctx.check_async_error()
-    counts = b.counts.cpu().numpy().view(np.uint32).copy()
-    pts = b.points.cpu().numpy()
-    idx = b.index.cpu().numpy().view(np.uint32) if want_index else None
-    return pts, idx, counts, b.roi_n
 
 
 def line_distance(got, want_bits):
@@ -282,40 +263,6 @@ def compact_frames(p):
     if len(fr) == 1:
         fr += [np.ascontiguousarray(fr[0][::-1]), np.ascontiguousarray(fr[0][:, ::-1]), np.ascontiguousarray(fr[0][::-1, ::-1])]
     return fr
-
-
-def check_compact_is_filtered_parity(ctx, algo, frames, dmin, want_index, what, scale=1.0, decoded=None):
-    """Points, indices and counts of a COMPACT launch against the SAME context's PARITY launch filtered on the host by
-    isfinite(X) & isfinite(Y) & isfinite(Z) & !(d <= min_disparity), in order -- exactly what the w_safe shortcut of
-    the count predicates promises, and no oracle involved.  The COMPACT launch must have been served by `algo`: the
-    single pass (2) and the resident blocks (3) count their launches, a re-route to the two-pass form does not."""
-    ctx.set_min_disparity(dmin)
-    ctx.set_mode(d2pc.MODE_PARITY)
-    full, _, _, roi_n = run_batch(ctx, frames, want_index=False, scale=scale)
-    ctx.set_mode(d2pc.MODE_COMPACT)
-    st0 = ctx.compact_stats()
-    pts, idx, counts, _ = run_batch(ctx, frames, want_index=want_index, scale=scale)
-    st = ctx.compact_stats()
-    assert st["timeouts"] == st0["timeouts"], what
-    if algo in (2, 3):
-        assert st["launches"] == st0["launches"] + 1 and st["twopass_fallbacks"] == st0["twopass_fallbacks"], (what, st0, st)
-    else:
-        assert st["launches"] == st0["launches"], (what, st0, st)
-    assert not np.any(counts == 0xFFFFFFFF), what
-    h, w = frames[0].shape
-    b = ctx.config().border
-    v, u = np.mgrid[b:h - b, b:w - b]
-    pix = (v * w + u).reshape(-1).astype(np.uint32)
-    for f in range(len(frames)):
-        d = (decoded if decoded is not None else frames)[f][b:h - b, b:w - b].reshape(-1)
-        fp = full[f, :roi_n]
-        keep = np.isfinite(fp[:, :3]).all(axis=1) & ~(d <= np.float32(dmin))
-        assert counts[f] == keep.sum(), f"{what} frame {f}: count {counts[f]} != {keep.sum()}"
-        n = int(counts[f])
-        assert np.array_equal(pts[f, :n].view(np.uint32), fp[keep].view(np.uint32)), f"{what} frame {f}: points"
-        if want_index:
-            assert np.array_equal(idx[f, :n], pix[keep]), f"{what} frame {f}: indices"
-    return pts, idx, counts
 
 
 @pytest.mark.parametrize("name,shape", ALL)

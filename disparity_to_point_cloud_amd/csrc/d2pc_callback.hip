@@ -15,6 +15,85 @@
 namespace d2pc {
 
 // --------------------------------------------------------------------------
+// The per-pixel pieces the three kernels below share.
+// --------------------------------------------------------------------------
+// Per byte value: 1/W, Z and (COMPACT) the validity class of the point: 0 dropped, 1 kept, 2 = only the arithmetic can tell.
+// Where the tables live is the kernel's choice.
+struct CbTables {
+  double *iw;    // [256]
+  float *z;      // [256]
+  uint8_t *cls;  // [256], nullptr in PARITY
+};
+
+// One thread per byte value fills its entry (stereo Q only) and returns its class (CLS; 0 otherwise).
+template <int QK, bool CLS>
+__device__ __forceinline__ uint32_t cb_fill_tables(uint32_t tid, const Geom &g, const QArg<QK> &Q, const CbTables &lut) {
+  const float d = __fmul_rn(float(tid), g.scale);  // cpp:61, as load_disparity<DT_U8>
+  const float dsel = fabsf(d) < __builtin_huge_valf() ? d : __builtin_nanf("");
+  const double nw = stereo_w(Q, double(dsel));
+  const double iw = 1.0 / nw;
+  lut.iw[tid] = iw;
+  lut.z[tid] = big_z_rule(d, float(Q.s.f * iw));
+  if constexpr (CLS) {
+    // the single pass's predicate (tile_count): finite, non-zero W of at least w_safe => every coordinate finite
+    const bool fin = finite_nonzero(nw), big = fabs(nw) >= Q.s.w_safe, keep = !(d <= g.min_disparity);
+    const uint32_t cls = fin && keep ? (big ? 1u : 2u) : 0u;
+    lut.cls[tid] = uint8_t(cls);
+    return cls;
+  } else {
+    return 0u;
+  }
+}
+
+// One pixel in COMPACT mode: its point (when wanted) and whether it survives.  `exact` is block-uniform: the count and the
+// scatter decide every pixel the same way.
+template <int QK>
+__device__ __forceinline__ bool cb_pixel(const QArg<QK> &Q, const Geom &g, const CbTables &lut, uint32_t x, uint32_t y, uint32_t raw,
+                                         double xs, double ys, bool exact, bool want_point, float &X, float &Y, float &Z) {
+  if constexpr (is_stereo(QK)) {
+    if (!exact && !want_point) return lut.cls[raw] == 1u;
+    const double iw = lut.iw[raw];
+    X = float(xs * iw);
+    Y = float(ys * iw);
+    Z = lut.z[raw];
+    if (!exact) return lut.cls[raw] == 1u;
+    return point_is_valid(X, Y, Z, __fmul_rn(float(raw), g.scale), g.min_disparity);
+  } else {
+    const float d = __fmul_rn(float(raw), g.scale);
+    reproject(Q, x, y, d, X, Y, Z);
+    return point_is_valid(X, Y, Z, d, g.min_disparity);
+  }
+}
+
+// One 64-column step of a row's ordered stores: the survivors' ranks behind row_pos (ballot + mbcnt), their points and
+// indices; row_pos moves past them.
+__device__ __forceinline__ void cb_store_step(const Geom &g, float4 *fout, uint32_t *fidx, bool ok, uint32_t x, uint32_t y, float X, float Y,
+                                              float Z, uint32_t &row_pos) {
+  const uint64_t m = __ballot(ok);
+  const uint32_t pos = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), row_pos));
+  // pos < roi_n always holds for a correct prefix; the guard keeps a timed-out prefix from becoming an out-of-bounds store
+  if (ok && pos < g.roi_n) {
+    store_point<D2PC_CB_STORE_NT != 0>(fout, pos, X, Y, Z);
+    if (fidx) st<D2PC_CB_INDEX_NT != 0>(fidx + pos, y * g.width + x);
+  }
+  row_pos += uint32_t(__popcll(m));
+}
+
+// A row of the tile through the exact / general-Q path: the same decisions as the count, the points, their ordered stores.
+template <int QK>
+__device__ __forceinline__ void cb_scatter_row(const QArg<QK> &Q, const Geom &g, const CbTables &lut, float4 *fout, uint32_t *fidx,
+                                               uint32_t x0, uint32_t x_end, uint32_t y, uint32_t lane, const uint32_t (&raw)[4],
+                                               const double (&xs)[4], double ys, bool exact, uint32_t row_pos) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint32_t x = x0 + 64u * uint32_t(q) + lane;
+    float X, Y, Z;
+    const bool ok = cb_pixel(Q, g, lut, x, y, raw[q], xs[q], ys, exact, true, X, Y, Z) && x < x_end;
+    cb_store_step(g, fout, fidx, ok, x, y, X, Y, Z, row_pos);
+  }
+}
+
+// --------------------------------------------------------------------------
 // K1g: the callback body TILE BY TILE -- bit-sliced k x k median of a 256 x 32 tile of the inset ROI
 // (d2pc_median_bs_tile.hpp, cpp:55-57) and, from the filtered bytes still in LDS, the tile's points
 // (cpp:60-85, PARITY).  No hand-off between blocks and no filtered image in memory: the VALU-bound filter
@@ -50,15 +129,10 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
 
   // (round 6: the table in 3 KB of its own, filled under the tile's loads instead of here behind a barrier: no difference --
   //  562.7 against 562.5 us, profiles/r06_ab_callback_prio.txt; under the power cap a shorter stage buys nothing by itself)
-  double *lut_iw = reinterpret_cast<double *>(s_raw);              // [256]
-  float *lut_z = reinterpret_cast<float *>(s_raw) + 2 * 256;       // [256]
+  const CbTables lut{reinterpret_cast<double *>(s_raw), reinterpret_cast<float *>(s_raw) + 2 * 256, nullptr};
   static_assert(S::RAW_WORDS >= 3 * 256, "the table fits where the staged rows were");
   if constexpr (is_stereo(QK)) {
-    const float d = __fmul_rn(float(tid), g.scale);  // cpp:61, as load_disparity<DT_U8>
-    const float dsel = fabsf(d) < __builtin_huge_valf() ? d : __builtin_nanf("");
-    const double iw = 1.0 / stereo_w(Q, double(dsel));
-    lut_iw[tid] = iw;
-    lut_z[tid] = big_z_rule(d, float(Q.s.f * iw));
+    cb_fill_tables<QK, false>(tid, g, Q, lut);
     __syncthreads();
   }
   const uint8_t *ob = reinterpret_cast<const uint8_t *>(s_w);
@@ -92,10 +166,10 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
       const uint32_t x = x0 + 64u * uint32_t(q) + lane;
       float X, Y, Z;
       if constexpr (is_stereo(QK)) {
-        const double iw = lut_iw[raw[q]];
+        const double iw = lut.iw[raw[q]];
         X = float(xs[q] * iw);
         Y = float(ys * iw);
-        Z = lut_z[raw[q]];
+        Z = lut.z[raw[q]];
       } else {
         reproject(Q, x, y, __fmul_rn(float(raw[q]), g.scale), X, Y, Z);
       }
@@ -156,26 +230,137 @@ struct CbCompactState {
     row_cnt = reinterpret_cast<uint32_t *>(fs + kCbTicketBytes + cb_band_acc_bytes(tiles_y));
   }
 };
+using cb_gu32 = __attribute__((address_space(1))) uint32_t;
+using cb_gu64 = __attribute__((address_space(1))) uint64_t;
+
+// Publish a tile (one wave): its 32 row counts from s_cnt as sixteen tagged dwords, {1, tile total} onto its band's accumulator.
+__device__ __forceinline__ void cb_publish(const CbCompactState &cs, uint32_t tile, uint32_t ty, const uint32_t *s_cnt, uint32_t *s_stat,
+                                           uint32_t lane) {
+  const uint32_t mine = lane < 32u ? s_cnt[lane] : 0u;
+  const uint32_t tile_total = wave_sum(mine);
+  if (lane < 16u)
+    __hip_atomic_store((cb_gu32 *)(cs.row_cnt + tile * 16u + lane), kCbRowTag | s_cnt[2u * lane] | (s_cnt[2u * lane + 1u] << 9),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (lane == 0) {
+    __hip_atomic_fetch_add((cb_gu64 *)(cs.band_acc + ty), (uint64_t(1) << 32) | tile_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if D2PC_ONEPASS_STATS
+    s_stat[0] += 1u;
+#endif
+  }
+}
+
+// What places a tile, per lane before the reduction: survivors of the bands above; of lane (j, p)'s two rows 2p, 2p + 1 over
+// the band's tiles j, j + 4, ... (t0, t1) and over those of them left of the tile (l0, l1).
+struct CbSums {
+  uint32_t above = 0, t0 = 0, t1 = 0, l0 = 0, l1 = 0;
+  // each returns whether the word was final
+  __device__ __forceinline__ bool add_band(uint64_t v, uint32_t tiles_x) {
+    above += uint32_t(v);
+    return uint32_t(v >> 32) == tiles_x;
+  }
+  __device__ __forceinline__ bool add_rows(uint32_t v, bool left) {
+    const uint32_t c0 = v & 0x1ffu, c1 = (v >> 9) & 0x1ffu;
+    t0 += c0, t1 += c1;
+    if (left) l0 += c0, l1 += c1;
+    return (v & kCbRowTag) != 0u;
+  }
+};
+
+// One pass = the accumulators of the bands above (64 per step) and the band's row-count words (lane = (j, p):
+// tiles j, j + 4, ..., row pair p), all requested together; true when every word of this lane was complete.
+__device__ __forceinline__ bool cb_look(const CbCompactState &cs, const MedianArgs &ma, uint32_t ty, uint32_t tx, uint32_t lane, CbSums &s) {
+  const uint32_t j = lane >> 4, p = lane & 15u;
+  bool ok = true;
+  s = CbSums{};
+  for (uint32_t b0 = 0; b0 < ty; b0 += 64u) {
+    const uint32_t bi = b0 + lane;
+    if (bi < ty)
+      ok = s.add_band(__hip_atomic_load((cb_gu64 *)(cs.band_acc + bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ma.tiles_x) && ok;
+  }
+  for (uint32_t k = j; k < ma.tiles_x; k += 4u)
+    ok = s.add_rows(__hip_atomic_load((cb_gu32 *)(cs.row_cnt + (ty * ma.tiles_x + k) * 16u + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
+                    k < tx) && ok;
+  return ok;
+}
+
+// Wait (one wave) until a look has found every word complete -- `ok` is the first look's answer, the caller's -- then place the
+// tile's rows: the per-row bases into s_base and, from the frame's last band, the frame's count.
+__device__ __forceinline__ void cb_wait_and_place(const CbCompactState &cs, StateHeader *hdr, const MedianArgs &ma, const Geom &g,
+                                                  uint32_t *counts, uint32_t f, uint32_t ty, uint32_t tx, uint32_t lane, CbSums s, bool ok,
+                                                  uint32_t *s_base, uint32_t *s_stat) {
+  uint32_t spins = 0;
+  uint64_t w0 = 0;
+  while (!__all(ok)) {
+    if (spins == 0) w0 = __builtin_amdgcn_s_memrealtime();
+    backoff(spins);
+    ++spins;
+    if ((spins & 7u) == 0 && wait_gave_up(hdr, lane, w0, g.spin_ticks)) break;
+    ok = cb_look(cs, ma, ty, tx, lane, s);
+  }
+#if D2PC_ONEPASS_STATS
+  if (spins && lane == 0) {
+    s_stat[1] += spins;
+    s_stat[2] += uint32_t(__builtin_amdgcn_s_memrealtime() - w0);
+  }
+#endif
+  const uint32_t above = wave_sum(s.above);
+#pragma unroll
+  for (int o = 16; o <= 32; o <<= 1) {
+    s.t0 += __shfl_xor(s.t0, o, 64), s.t1 += __shfl_xor(s.t1, o, 64);
+    s.l0 += __shfl_xor(s.l0, o, 64), s.l1 += __shfl_xor(s.l1, o, 64);
+  }
+  // lanes 0..15 hold the row pairs; spread to one row per lane: row r = 2p + h comes from lane p
+  const uint32_t src_lane = (lane & 31u) >> 1;
+  const uint32_t tt0 = __shfl(s.t0, src_lane, 64), tt1 = __shfl(s.t1, src_lane, 64);
+  const uint32_t ll0 = __shfl(s.l0, src_lane, 64), ll1 = __shfl(s.l1, src_lane, 64);
+  const uint32_t row_total = lane < 32u ? ((lane & 1u) ? tt1 : tt0) : 0u;
+  const uint32_t row_left = (lane & 1u) ? ll1 : ll0;
+  uint32_t incl = row_total;
+#pragma unroll
+  for (int o = 1; o < 32; o <<= 1) {
+    const uint32_t n = __shfl_up(incl, o, 64);
+    if (lane >= uint32_t(o)) incl += n;
+  }
+  if (lane < 32u) s_base[lane] = above + incl - row_total + row_left;
+  const uint32_t band_total = __builtin_amdgcn_readlane(incl, 31);
+  if (counts && ty == ma.tiles_y - 1u && tx == 0u && lane == 0u) {
+    const bool bad = __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+    __hip_atomic_store(counts + f, bad ? kCountTimedOut : above + band_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// The end of a block (one thread): a block that saw the launch break marks its frame, whether or not the frame's last tile
+// has reported already; then what its waits cost goes to the block's slot of the counters.
+__device__ __forceinline__ void cb_block_end(StateHeader *hdr, uint32_t *counts, uint32_t f, const uint32_t *s_stat, uint32_t block) {
+  if (counts && __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+    __hip_atomic_store(counts + f, kCountTimedOut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#if D2PC_ONEPASS_STATS
+  CompactStats::Slot *sl = hdr->stats->slot + (block % uint32_t(kStatSlots));
+  atomicAdd(&sl->tiles, (unsigned long long)s_stat[0]);
+  if (s_stat[1]) {
+    atomicAdd(&sl->failed_polls, (unsigned long long)s_stat[1]);
+    atomicAdd(&sl->wait_ticks, (unsigned long long)s_stat[2]);
+  }
+#endif
+}
 
 template <int KS, int QK>
 __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_waves_per_eu(D2PC_BS_WAVES))) void k_callback_bs_compact(
     const uint8_t *__restrict__ src, float4 *__restrict__ out, uint32_t *__restrict__ out_index, uint32_t *__restrict__ counts,
     uint8_t *state, const MedianArgs ma, const Geom g, const QArg<QK> Q) {
   using S = MedianBsShape<KS>;
-  using gu32 = __attribute__((address_space(1))) uint32_t;
-  using gu64 = __attribute__((address_space(1))) uint64_t;
   static_assert(S::THREADS == 256 && S::TH == 32, "one thread per byte value fills the table; 32 row counts per tile");
   __shared__ __attribute__((aligned(16))) uint32_t s_w[S::W_WORDS];
   __shared__ __attribute__((aligned(16))) uint32_t s_raw[S::RAW_WORDS];
   __shared__ uint32_t s_tile, s_exact;
   __shared__ uint32_t s_cnt[32], s_base[32];
   __shared__ uint32_t s_stat[3];
-  // per byte value: 1/W, Z and the validity class of the point (0 dropped, 1 kept, 2 = only the arithmetic can tell).
   // Tables of their own (not in the staged rows' space as in k_callback_bs): they are filled while the ticket's
   // atomic is in flight
   __shared__ double lut_iw[256];
   __shared__ float lut_z[256];
   __shared__ uint8_t lut_cls[256];
+  const CbTables lut{lut_iw, lut_z, lut_cls};
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   StateHeader *hdr = reinterpret_cast<StateHeader *>(state);
   const uint32_t f = blockIdx.x % g.n_frames;  // the grid is tiles_per_frame * n_frames: every frame gets its tiles' worth of blocks
@@ -187,16 +372,7 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
   }
   if (tid < 3) s_stat[tid] = 0;
   if constexpr (is_stereo(QK)) {
-    const float d = __fmul_rn(float(tid), g.scale);  // cpp:61, as load_disparity<DT_U8>
-    const float dsel = fabsf(d) < __builtin_huge_valf() ? d : __builtin_nanf("");
-    const double nw = stereo_w(Q, double(dsel));
-    const double iw = 1.0 / nw;
-    lut_iw[tid] = iw;
-    lut_z[tid] = big_z_rule(d, float(Q.s.f * iw));
-    // the single pass's predicate (tile_count): finite, non-zero W of at least w_safe => every coordinate finite
-    const bool fin = finite_nonzero(nw), big = fabs(nw) >= Q.s.w_safe, keep = !(d <= g.min_disparity);
-    const uint32_t cls = fin && keep ? (big ? 1u : 2u) : 0u;
-    lut_cls[tid] = uint8_t(cls);
+    const uint32_t cls = cb_fill_tables<QK, true>(tid, g, Q, lut);
     __syncthreads();                  // (s_exact's initial value is in place)
     if (cls == 2u) s_exact = 1u;      // (benign race: every writer stores 1)
   }
@@ -216,22 +392,6 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
     xs[q] = 0.0;
     if constexpr (is_stereo(QK)) xs[q] = stereo_nx(Q, x0 + 64u * uint32_t(q) + lane);
   }
-  // one pixel: its point (when wanted) and whether it survives
-  auto pixel = [&](uint32_t x, uint32_t y, uint32_t raw, int q, double ys, bool want_point, float &X, float &Y, float &Z) -> bool {
-    if constexpr (is_stereo(QK)) {
-      if (!exact && !want_point) return lut_cls[raw] == 1u;
-      const double iw = lut_iw[raw];
-      X = float(xs[q] * iw);
-      Y = float(ys * iw);
-      Z = lut_z[raw];
-      if (!exact) return lut_cls[raw] == 1u;
-      return point_is_valid(X, Y, Z, __fmul_rn(float(raw), g.scale), g.min_disparity);
-    } else {
-      const float d = __fmul_rn(float(raw), g.scale);
-      reproject(Q, x, y, d, X, Y, Z);
-      return point_is_valid(X, Y, Z, d, g.min_disparity);
-    }
-  };
 
   // ---- count: survivors per row of the tile (a wave takes every fourth row, 64 columns per step) ----------
 #pragma unroll 1
@@ -246,7 +406,7 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
         const uint32_t x = x0 + 64u * uint32_t(q) + lane;
         const uint32_t raw = ob[r * uint32_t(S::OUT_STRIDE) + 64u * uint32_t(q) + lane];
         float X, Y, Z;
-        const bool ok = pixel(x, y, raw, q, ys, false, X, Y, Z) && x < x_end;
+        const bool ok = cb_pixel(Q, g, lut, x, y, raw, xs[q], ys, exact, false, X, Y, Z) && x < x_end;
         cnt += uint32_t(__popcll(__ballot(ok)));
       }
     }
@@ -256,97 +416,16 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
 
   // ---- hand-off (wave 0): publish the 32 row counts, wait for the band and the bands above, place the rows ----
   if (wave == 0) {
-    const uint32_t mine = lane < 32u ? s_cnt[lane] : 0u;
-    const uint32_t tile_total = wave_sum(mine);
-    if (lane < 16u)
-      __hip_atomic_store((gu32 *)(cs.row_cnt + lt * 16u + lane), kCbRowTag | s_cnt[2u * lane] | (s_cnt[2u * lane + 1u] << 9),
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == 0)
-      __hip_atomic_fetch_add((gu64 *)(cs.band_acc + ty), (uint64_t(1) << 32) | tile_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // One pass = the accumulators of the bands above (64 per step) and the band's row-count words (lane = (j, p):
-    // tiles j, j + 4, ..., row pair p), all requested together; a pass in which every word is complete ends the wait.
-    const uint32_t j = lane >> 4, p = lane & 15u;
-    uint32_t above = 0, t0 = 0, t1 = 0, l0 = 0, l1 = 0, spins = 0;
-    uint64_t w0 = 0;
-    for (;;) {
-      bool ok = true;
-      above = 0;
-      for (uint32_t b0 = 0; b0 < ty; b0 += 64u) {
-        const uint32_t bi = b0 + lane;
-        if (bi < ty) {
-          const uint64_t v = __hip_atomic_load((gu64 *)(cs.band_acc + bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          ok = ok && uint32_t(v >> 32) == ma.tiles_x;
-          above += uint32_t(v);
-        }
-      }
-      t0 = t1 = l0 = l1 = 0;
-      for (uint32_t k = j; k < ma.tiles_x; k += 4u) {
-        const uint32_t v = __hip_atomic_load((gu32 *)(cs.row_cnt + (ty * ma.tiles_x + k) * 16u + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = ok && (v & kCbRowTag) != 0u;
-        const uint32_t c0 = v & 0x1ffu, c1 = (v >> 9) & 0x1ffu;
-        t0 += c0, t1 += c1;
-        if (k < tx) l0 += c0, l1 += c1;
-      }
-      if (__all(ok)) break;
-      if (spins == 0) w0 = __builtin_amdgcn_s_memrealtime();
-      backoff(spins);
-      ++spins;
-      // bounded by time, and over as soon as ANY wave of the launch has given up (sticky flag)
-      if ((spins & 7u) == 0 && (__builtin_amdgcn_s_memrealtime() - w0 > uint64_t(g.spin_ticks) ||
-                                __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-        if (lane == 0 && __hip_atomic_exchange(&hdr->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-          atomicAdd(&hdr->stats->timeouts, 1ull);
-        break;
-      }
-    }
-#if D2PC_ONEPASS_STATS
-    if (spins && lane == 0) {
-      s_stat[1] = spins;
-      s_stat[2] = uint32_t(__builtin_amdgcn_s_memrealtime() - w0);
-    }
-#endif
-    above = wave_sum(above);
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-      t0 += __shfl_xor(t0, o, 64), t1 += __shfl_xor(t1, o, 64);
-      l0 += __shfl_xor(l0, o, 64), l1 += __shfl_xor(l1, o, 64);
-    }
-    // lanes 0..15 hold the row pairs; spread to one row per lane: row r = 2p + h comes from lane p
-    const uint32_t src_lane = (lane & 31u) >> 1;
-    const uint32_t tt0 = __shfl(t0, src_lane, 64), tt1 = __shfl(t1, src_lane, 64);
-    const uint32_t ll0 = __shfl(l0, src_lane, 64), ll1 = __shfl(l1, src_lane, 64);
-    const uint32_t row_total = lane < 32u ? ((lane & 1u) ? tt1 : tt0) : 0u;
-    const uint32_t row_left = (lane & 1u) ? ll1 : ll0;
-    uint32_t incl = row_total;
-#pragma unroll
-    for (int o = 1; o < 32; o <<= 1) {
-      const uint32_t n = __shfl_up(incl, o, 64);
-      if (lane >= uint32_t(o)) incl += n;
-    }
-    if (lane < 32u) s_base[lane] = above + incl - row_total + row_left;
-    const uint32_t band_total = __builtin_amdgcn_readlane(incl, 31);
-    if (counts && ty == ma.tiles_y - 1u && tx == 0u && lane == 0u) {
-      const bool bad = __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-      __hip_atomic_store(counts + f, bad ? kCountTimedOut : above + band_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    cb_publish(cs, lt, ty, s_cnt, s_stat, lane);
+    CbSums sums;
+    const bool ok = cb_look(cs, ma, ty, tx, lane, sums);
+    cb_wait_and_place(cs, hdr, ma, g, counts, f, ty, tx, lane, sums, ok, s_base, s_stat);
   }
   __syncthreads();
 
-  if (tid == 0) {
-    // a block that saw the launch break marks its frame, whether or not the frame's last tile has reported already.
-    // (Here, not behind the stores: a barrier after them would hold every wave until its stores have drained,
-    // and the block could not make room for the next one while they do.)
-    if (counts && __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      __hip_atomic_store(counts + f, kCountTimedOut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if D2PC_ONEPASS_STATS
-    CompactStats::Slot *sl = hdr->stats->slot + (blockIdx.x % uint32_t(kStatSlots));
-    atomicAdd(&sl->tiles, 1ull);
-    if (s_stat[1]) {
-      atomicAdd(&sl->failed_polls, (unsigned long long)s_stat[1]);
-      atomicAdd(&sl->wait_ticks, (unsigned long long)s_stat[2]);
-    }
-#endif
-  }
+  // (Here, not behind the stores: a barrier after them would hold every wave until its stores have drained,
+  // and the block could not make room for the next one while they do.)
+  if (tid == 0) cb_block_end(hdr, counts, f, s_stat, blockIdx.x);
   // ---- scatter: the same decisions, the points, their ordered stores ------------------------------------
   float4 *fout = out + uint64_t(f) * g.out_frame_stride;
   uint32_t *fidx = out_index ? out_index + uint64_t(f) * g.out_frame_stride : nullptr;
@@ -354,26 +433,12 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
   for (uint32_t r = wave; r < uint32_t(S::TH); r += uint32_t(S::THREADS / 64)) {
     const uint32_t y = y0 + r;
     if (y >= y_end) break;
-    uint32_t row_pos = s_base[r];
     double ys = 0.0;
     if constexpr (is_stereo(QK)) ys = stereo_ny(Q, y);
     uint32_t raw[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) raw[q] = ob[r * uint32_t(S::OUT_STRIDE) + 64u * uint32_t(q) + lane];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const uint32_t x = x0 + 64u * uint32_t(q) + lane;
-      float X, Y, Z;
-      const bool ok = pixel(x, y, raw[q], q, ys, true, X, Y, Z) && x < x_end;
-      const uint64_t m = __ballot(ok);
-      const uint32_t pos = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), row_pos));
-      // pos < roi_n always holds for a correct prefix; the guard keeps a timed-out prefix from becoming an out-of-bounds store
-      if (ok && pos < g.roi_n) {
-        store_point<D2PC_CB_STORE_NT != 0>(fout, pos, X, Y, Z);
-        if (fidx) st<D2PC_CB_INDEX_NT != 0>(fidx + pos, y * g.width + x);
-      }
-      row_pos += uint32_t(__popcll(m));
-    }
+    cb_scatter_row(Q, g, lut, fout, fidx, x0, x_end, y, lane, raw, xs, ys, exact, s_base[r]);
   }
 }
 
@@ -392,8 +457,6 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
 // tile's band (up to 128 bands: two per lane) and the row counts of the band's tiles (lane = 16 j + p reads dword p of
 // tiles j, j + 4, ...: up to 4 per lane = 16 tiles across), requested in one place and examined in another.
 struct CbEarlyPlace {
-  using gu32 = __attribute__((address_space(1))) uint32_t;
-  using gu64 = __attribute__((address_space(1))) uint64_t;
   static constexpr int kBands = 2, kTiles = 4;  // (images up to 4,096 x 4,096 output pixels; larger ones poll as before)
   uint64_t band[kBands];
   uint32_t row[kTiles];
@@ -406,40 +469,27 @@ struct CbEarlyPlace {
 #pragma unroll
     for (int b = 0; b < kBands; ++b) {
       const uint32_t bi = 64u * uint32_t(b) + lane;
-      band[b] = bi < ty ? __hip_atomic_load((gu64 *)(cs.band_acc + bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+      band[b] = bi < ty ? __hip_atomic_load((cb_gu64 *)(cs.band_acc + bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
     }
 #pragma unroll
     for (int i = 0; i < kTiles; ++i) {
       const uint32_t k = j + 4u * uint32_t(i);
-      row[i] = k < ma.tiles_x ? __hip_atomic_load((gu32 *)(cs.row_cnt + (ty * ma.tiles_x + k) * 16u + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+      row[i] = k < ma.tiles_x ? __hip_atomic_load((cb_gu32 *)(cs.row_cnt + (ty * ma.tiles_x + k) * 16u + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     }
   }
-  // the same sums the polling loop forms; false when any word was not final yet (or nothing was requested)
-  __device__ __forceinline__ bool take(const MedianArgs &ma, uint32_t ty, uint32_t tx, uint32_t lane, uint32_t &above, uint32_t &t0,
-                                       uint32_t &t1, uint32_t &l0, uint32_t &l1) const {
+  // cb_look's sums from the words requested; false when any of them was not final yet (or nothing was requested)
+  __device__ __forceinline__ bool take(const MedianArgs &ma, uint32_t ty, uint32_t tx, uint32_t lane, CbSums &s) const {
     if (!fits) return false;
     const uint32_t j = lane >> 4;
     bool ok = true;
-    above = 0;
+    s = CbSums{};
 #pragma unroll
-    for (int b = 0; b < kBands; ++b) {
-      const uint32_t bi = 64u * uint32_t(b) + lane;
-      if (bi < ty) {
-        ok = ok && uint32_t(band[b] >> 32) == ma.tiles_x;
-        above += uint32_t(band[b]);
-      }
-    }
-    t0 = t1 = l0 = l1 = 0;
+    for (int b = 0; b < kBands; ++b)
+      if (64u * uint32_t(b) + lane < ty) ok = s.add_band(band[b], ma.tiles_x) && ok;
 #pragma unroll
     for (int i = 0; i < kTiles; ++i) {
       const uint32_t k = j + 4u * uint32_t(i);
-      if (k < ma.tiles_x) {
-        const uint32_t v = row[i];
-        ok = ok && (v & kCbRowTag) != 0u;
-        const uint32_t c0 = v & 0x1ffu, c1 = (v >> 9) & 0x1ffu;
-        t0 += c0, t1 += c1;
-        if (k < tx) l0 += c0, l1 += c1;
-      }
+      if (k < ma.tiles_x) ok = s.add_rows(row[i], k < tx) && ok;
     }
     return ok;
   }
@@ -450,8 +500,6 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
     const uint8_t *__restrict__ src, float4 *__restrict__ out, uint32_t *__restrict__ out_index, uint32_t *__restrict__ counts,
     uint8_t *state, const MedianArgs ma, const Geom g, const QArg<QK> Q) {
   using S = MedianBsShape<KS>;
-  using gu32 = __attribute__((address_space(1))) uint32_t;
-  using gu64 = __attribute__((address_space(1))) uint64_t;
   static_assert(S::THREADS == 256 && S::TH == 32, "one thread per byte value fills the table; 32 row counts per tile");
   constexpr uint32_t KEEP_WORDS = uint32_t(S::OUT_STRIDE * S::TH / 4);
   __shared__ __attribute__((aligned(16))) uint32_t s_w[S::W_WORDS];
@@ -470,9 +518,8 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
   float4 *fout = out + uint64_t(f) * g.out_frame_stride;
   uint32_t *fidx = out_index ? out_index + uint64_t(f) * g.out_frame_stride : nullptr;
   const uint32_t x_end = ma.out_x0 + ma.out_w, y_end = ma.out_y0 + ma.out_h;
-  double *lut_iw = reinterpret_cast<double *>(s_raw);               // [256]   (the staged rows' space, free between filters)
-  float *lut_z = reinterpret_cast<float *>(s_raw) + 2 * 256;        // [256]
-  uint8_t *lut_cls = reinterpret_cast<uint8_t *>(s_raw + 3 * 256);  // [256]
+  // (the staged rows' space, free between filters)
+  const CbTables lut{reinterpret_cast<double *>(s_raw), reinterpret_cast<float *>(s_raw) + 2 * 256, reinterpret_cast<uint8_t *>(s_raw + 3 * 256)};
   static_assert(S::RAW_WORDS >= 3 * 256 + 64, "the tables fit where the staged rows were");
 
 #ifdef D2PC_DIAG  // stage timers: tools/diag_callback.py
@@ -489,23 +536,6 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
   if (cur >= tpf) cur = kNoTile;
   bool exact = !is_stereo(QK);
 
-  // one pixel: its point (when wanted) and whether it survives
-  auto pixel = [&](uint32_t x, uint32_t y, uint32_t raw, double xs, double ys, bool want_point, float &X, float &Y, float &Z) -> bool {
-    if constexpr (is_stereo(QK)) {
-      if (!exact && !want_point) return lut_cls[raw] == 1u;
-      const double iw = lut_iw[raw];
-      X = float(xs * iw);
-      Y = float(ys * iw);
-      Z = lut_z[raw];
-      if (!exact) return lut_cls[raw] == 1u;
-      return point_is_valid(X, Y, Z, __fmul_rn(float(raw), g.scale), g.min_disparity);
-    } else {
-      const float d = __fmul_rn(float(raw), g.scale);
-      reproject(Q, x, y, d, X, Y, Z);
-      return point_is_valid(X, Y, Z, d, g.min_disparity);
-    }
-  };
-
   while (cur != kNoTile || prev != kNoTile) {
     // Everything derived from the thread index is formed AGAIN in every iteration (opaque: the compiler cannot relate this
     // `tid` to the loop-invariant one).  Left to itself it hoists those values out of the loop -- the staging offsets of the
@@ -513,7 +543,9 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
     // the 168 that three waves per SIMD leave, parks them in scratch: 23-29 spilled VGPRs, ~25 scratch reloads per tile, each
     // a dependent round trip in front of the loads and table stores it feeds.  One fp64 division per thread and TILE is
     // cheaper: 16 x 4K with 30 % zero pixels + indices 766.8 -> 723.5 us (blocky), 813.9 -> 772.5 (iid), interleaved on one
-    // device (profiles/r05_ab_callback_nohoist.txt); 0 spilled VGPRs, 0 bytes of scratch (round 4's verdict, item 3a).
+    // device (profiles/r05_ab_callback_nohoist.txt).  That round's toolchain then reported 0 spilled VGPRs and 0 bytes of scratch
+    // (round 4's verdict, item 3a); the present one reports, for k = 11 only, 168 VGPRs with 2 to 6 of them spilled and 12 to
+    // 20 bytes of scratch per lane, and none for k <= 9 (profiles/callback_handoff_refactor_resources.txt).
     const uint32_t tid = opaque(tid0), lane = tid & 63u;
     uint32_t tk = 0, nxt = kNoTile;
     CbEarlyPlace early{};  // (born in the iteration: nothing of it is alive across the filter)
@@ -537,17 +569,8 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
       // the words that place `prev` are requested HERE by wave 0 and looked at behind the count: their round trip runs
       // under the table, the count and two (LDS-only) barriers instead of in front of the scatter with three waves waiting
       if (wave == 0 && prev != kNoTile) early.request(cs, ma, prev, lane);
-      if constexpr (is_stereo(QK)) {  // per byte value: 1/W, Z and the validity class (see K1c)
-        const float d = __fmul_rn(float(tid), g.scale);
-        const float dsel = fabsf(d) < __builtin_huge_valf() ? d : __builtin_nanf("");
-        const double nw = stereo_w(Q, double(dsel));
-        const double iw = 1.0 / nw;
-        lut_iw[tid] = iw;
-        lut_z[tid] = big_z_rule(d, float(Q.s.f * iw));
-        const bool fin = finite_nonzero(nw), big = fabs(nw) >= Q.s.w_safe, keep = !(d <= g.min_disparity);
-        const uint32_t cls = fin && keep ? (big ? 1u : 2u) : 0u;
-        lut_cls[tid] = uint8_t(cls);
-        if (cls == 2u) s_exact = 1u;  // (benign race: every writer stores 1; never reset)
+      if constexpr (is_stereo(QK)) {
+        if (cb_fill_tables<QK, true>(tid, g, Q, lut) == 2u) s_exact = 1u;  // (benign race: every writer stores 1; never reset)
       }
       lds_barrier();
 #ifdef D2PC_DIAG
@@ -575,7 +598,7 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
 #pragma unroll
         for (int i = 0; i < RPW; ++i)
 #pragma unroll
-          for (int b = 0; b < 4; ++b) cl[i][b] = lut_cls[(wrd[i] >> (8 * b)) & 0xffu];
+          for (int b = 0; b < 4; ++b) cl[i][b] = lut.cls[(wrd[i] >> (8 * b)) & 0xffu];
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int i = 0; i < RPW; ++i) {
@@ -600,7 +623,7 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
               double xs = 0.0;
               if constexpr (is_stereo(QK)) xs = stereo_nx(Q, x);
               float X, Y, Z;
-              const bool ok = pixel(x, y, raw, xs, ys, false, X, Y, Z) && x < x_end;
+              const bool ok = cb_pixel(Q, g, lut, x, y, raw, xs, ys, exact, false, X, Y, Z) && x < x_end;
               cnt += uint32_t(__popcll(__ballot(ok)));
             }
           }
@@ -616,19 +639,7 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
       // ---- publish `cur` (wave 1): sixteen tagged dwords + the band's accumulator; nothing to wait for.  Not wave 0: it
       // places `prev` at the same time, and a wave's vector memory operations retire in order -- the words it requested
       // for that would wait for these stores' acknowledgement ------
-      if (wave == 1u) {
-        const uint32_t mine = lane < 32u ? s_cnt[lane] : 0u;
-        const uint32_t tile_total = wave_sum(mine);
-        if (lane < 16u)
-          __hip_atomic_store((gu32 *)(cs.row_cnt + cur * 16u + lane), kCbRowTag | s_cnt[2u * lane] | (s_cnt[2u * lane + 1u] << 9),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (lane == 0) {
-          __hip_atomic_fetch_add((gu64 *)(cs.band_acc + ty), (uint64_t(1) << 32) | tile_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if D2PC_ONEPASS_STATS
-          s_stat[0] += 1u;
-#endif
-        }
-      }
+      if (wave == 1u) cb_publish(cs, cur, ty, s_cnt, s_stat, lane);
     }
 #ifdef D2PC_DIAG
     unsigned long long f5 = __builtin_amdgcn_s_memtime();
@@ -638,76 +649,10 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
       const uint32_t ty = prev / ma.tiles_x, tx = prev - ty * ma.tiles_x;
       const uint32_t x0 = ma.out_x0 + tx * uint32_t(S::TW), y0 = ma.out_y0 + ty * uint32_t(S::TH);
       if (wave == 0) {
-        const uint32_t j = lane >> 4, p = lane & 15u;
-        uint32_t above = 0, t0 = 0, t1 = 0, l0 = 0, l1 = 0, spins = 0;
-        uint64_t w0 = 0;
-        bool first = cur != kNoTile;  // (the last tile of a block has no filter in front of its placing: nothing was requested)
-        for (;;) {
-          bool ok = true;
-          above = 0;
-          if (first) {
-            first = false;
-            ok = early.take(ma, ty, tx, lane, above, t0, t1, l0, l1);
-            if (__all(ok)) break;
-            goto look_again;
-          }
-          for (uint32_t b0 = 0; b0 < ty; b0 += 64u) {
-            const uint32_t bi = b0 + lane;
-            if (bi < ty) {
-              const uint64_t v = __hip_atomic_load((gu64 *)(cs.band_acc + bi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              ok = ok && uint32_t(v >> 32) == ma.tiles_x;
-              above += uint32_t(v);
-            }
-          }
-          t0 = t1 = l0 = l1 = 0;
-          for (uint32_t k = j; k < ma.tiles_x; k += 4u) {
-            const uint32_t v = __hip_atomic_load((gu32 *)(cs.row_cnt + (ty * ma.tiles_x + k) * 16u + p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ok = ok && (v & kCbRowTag) != 0u;
-            const uint32_t c0 = v & 0x1ffu, c1 = (v >> 9) & 0x1ffu;
-            t0 += c0, t1 += c1;
-            if (k < tx) l0 += c0, l1 += c1;
-          }
-          if (__all(ok)) break;
-        look_again:
-          if (spins == 0) w0 = __builtin_amdgcn_s_memrealtime();
-          backoff(spins);
-          ++spins;
-          if ((spins & 7u) == 0 && (__builtin_amdgcn_s_memrealtime() - w0 > uint64_t(g.spin_ticks) ||
-                                    __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            if (lane == 0 && __hip_atomic_exchange(&hdr->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-              atomicAdd(&hdr->stats->timeouts, 1ull);
-            break;
-          }
-        }
-#if D2PC_ONEPASS_STATS
-        if (spins && lane == 0) {
-          s_stat[1] += spins;
-          s_stat[2] += uint32_t(__builtin_amdgcn_s_memrealtime() - w0);
-        }
-#endif
-        above = wave_sum(above);
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-          t0 += __shfl_xor(t0, o, 64), t1 += __shfl_xor(t1, o, 64);
-          l0 += __shfl_xor(l0, o, 64), l1 += __shfl_xor(l1, o, 64);
-        }
-        const uint32_t src_lane = (lane & 31u) >> 1;
-        const uint32_t tt0 = __shfl(t0, src_lane, 64), tt1 = __shfl(t1, src_lane, 64);
-        const uint32_t ll0 = __shfl(l0, src_lane, 64), ll1 = __shfl(l1, src_lane, 64);
-        const uint32_t row_total = lane < 32u ? ((lane & 1u) ? tt1 : tt0) : 0u;
-        const uint32_t row_left = (lane & 1u) ? ll1 : ll0;
-        uint32_t incl = row_total;
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-          const uint32_t n = __shfl_up(incl, o, 64);
-          if (lane >= uint32_t(o)) incl += n;
-        }
-        if (lane < 32u) s_base[lane] = above + incl - row_total + row_left;
-        const uint32_t band_total = __builtin_amdgcn_readlane(incl, 31);
-        if (counts && ty == ma.tiles_y - 1u && tx == 0u && lane == 0u) {
-          const bool bad = __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-          __hip_atomic_store(counts + f, bad ? kCountTimedOut : above + band_total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        CbSums sums;
+        // (the last tile of a block has no filter in front of its placing: nothing was requested, it looks at once)
+        const bool ok = cur != kNoTile ? early.take(ma, ty, tx, lane, sums) : cb_look(cs, ma, ty, tx, lane, sums);
+        cb_wait_and_place(cs, hdr, ma, g, counts, f, ty, tx, lane, sums, ok, s_base, s_stat);
       }
       lds_barrier();
 #ifdef D2PC_DIAG
@@ -732,7 +677,7 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
         uint32_t raw[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) raw[q] = kb[r * uint32_t(S::OUT_STRIDE) + 64u * uint32_t(q) + lane];
-        // the usual case (a calibrated Q, no sliver): the row's twelve table reads in flight together behind scheduling fences
+        // the usual path (a calibrated Q, no sliver): the row's twelve table reads in flight together behind scheduling fences
         // (see the count phase), the products only where a point is stored: -1 % of the launch (r05_ab_callback_stages.txt)
         if constexpr (is_stereo(QK)) if (!exact) {
           double t_iw[4];
@@ -741,9 +686,9 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
           asm volatile("" ::: "memory");
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            t_iw[q] = lut_iw[raw[q]];
-            t_z[q] = lut_z[raw[q]];
-            t_cls[q] = lut_cls[raw[q]];
+            t_iw[q] = lut.iw[raw[q]];
+            t_z[q] = lut.z[raw[q]];
+            t_cls[q] = lut.cls[raw[q]];
           }
           asm volatile("" ::: "memory");
 #pragma unroll
@@ -751,31 +696,11 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
             const uint32_t x = x0 + 64u * uint32_t(q) + lane;
             const float X = float(xs4[q] * t_iw[q]), Y = float(ys * t_iw[q]), Z = t_z[q];
             const bool ok = t_cls[q] == 1u && x < x_end;
-            const uint64_t m = __ballot(ok);
-            const uint32_t pos = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), row_pos));
-            if (ok && pos < g.roi_n) {
-              store_point<D2PC_CB_STORE_NT != 0>(fout, pos, X, Y, Z);
-              if (fidx) st<D2PC_CB_INDEX_NT != 0>(fidx + pos, y * g.width + x);
-            }
-            row_pos += uint32_t(__popcll(m));
+            cb_store_step(g, fout, fidx, ok, x, y, X, Y, Z, row_pos);
           }
           continue;
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t x = x0 + 64u * uint32_t(q) + lane;
-          double xs = 0.0;
-          if constexpr (is_stereo(QK)) xs = stereo_nx(Q, x);
-          float X, Y, Z;
-          const bool ok = pixel(x, y, raw[q], xs, ys, true, X, Y, Z) && x < x_end;
-          const uint64_t m = __ballot(ok);
-          const uint32_t pos = __builtin_amdgcn_mbcnt_hi(uint32_t(m >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(m), row_pos));
-          if (ok && pos < g.roi_n) {  // (the guard keeps a timed-out prefix from becoming an out-of-bounds store)
-            store_point<D2PC_CB_STORE_NT != 0>(fout, pos, X, Y, Z);
-            if (fidx) st<D2PC_CB_INDEX_NT != 0>(fidx + pos, y * g.width + x);
-          }
-          row_pos += uint32_t(__popcll(m));
-        }
+        cb_scatter_row(Q, g, lut, fout, fidx, x0, x_end, y, lane, raw, xs4, ys, exact, row_pos);
       }
     }
 #ifdef D2PC_DIAG
@@ -810,25 +735,15 @@ __global__ __launch_bounds__(MedianBsShape<KS>::THREADS) __attribute__((amdgpu_w
     if (tid == 0) atomicAdd(&g_bs_diag[blockIdx.x & 255u][7], (unsigned long long)(__builtin_amdgcn_s_memrealtime() - diag_r0));
   }
 #endif
-  if (tid == 0) {
-    // a block that saw the launch break marks its frame, whether or not the frame's last tile has reported already
-    if (counts && __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-      __hip_atomic_store(counts + f, kCountTimedOut, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if D2PC_ONEPASS_STATS
-    CompactStats::Slot *sl = hdr->stats->slot + (blockIdx.x % uint32_t(kStatSlots));
-    atomicAdd(&sl->tiles, (unsigned long long)s_stat[0]);
-    if (s_stat[1]) {
-      atomicAdd(&sl->failed_polls, (unsigned long long)s_stat[1]);
-      atomicAdd(&sl->wait_ticks, (unsigned long long)s_stat[2]);
-    }
-#endif
-  }
+  if (tid == 0) cb_block_end(hdr, counts, f, s_stat, blockIdx.x);
 }
 
 // --------------------------------------------------------------------------
 // launchers
 // --------------------------------------------------------------------------
-hipError_t launch_callback_bs(const LaunchArgs &a, MedianArgs m, const void *src, int ksize) {
+// What both launchers ask of a launch: the filter's output rectangle is the reprojection's ROI.  Fills m's tiles and
+// returns the number of tiles of the launch in `blocks`.
+static hipError_t cb_resolve_tiles(const LaunchArgs &a, MedianArgs &m, int ksize, uint64_t &blocks) {
   if (!median_ksize_supported(ksize) || m.out_w == 0 || m.out_h == 0) return hipErrorInvalidValue;
   if (m.out_x0 != a.geom.border || m.out_y0 != a.geom.border || m.out_w != a.geom.roi_w ||
       uint64_t(m.out_w) * m.out_h != a.geom.roi_n)
@@ -836,39 +751,24 @@ hipError_t launch_callback_bs(const LaunchArgs &a, MedianArgs m, const void *src
   using S = MedianBsShape<11>;  // the tile shape does not depend on k
   m.tiles_x = (m.out_w + S::TW - 1) / S::TW;
   m.tiles_y = (m.out_h + S::TH - 1) / S::TH;
-  const uint64_t blocks = uint64_t(m.tiles_x) * m.tiles_y * m.n_frames;
+  blocks = uint64_t(m.tiles_x) * m.tiles_y * m.n_frames;
   if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+  return hipSuccess;
+}
+
+hipError_t launch_callback_bs(const LaunchArgs &a, MedianArgs m, const void *src, int ksize) {
+  uint64_t blocks = 0;
+  if (hipError_t e = cb_resolve_tiles(a, m, ksize, blocks); e != hipSuccess) return e;
   const uint8_t *s8 = static_cast<const uint8_t *>(src);
   float4 *o = static_cast<float4 *>(a.out_points);
-#define D2PC_CB_BS(KS, QK)                                                                                              \
-  hipLaunchKernelGGL((k_callback_bs<KS, QK>), dim3(uint32_t(blocks)), dim3(S::THREADS), D2PC_CB_LDS_PAD, a.stream, s8, o, a.out_index, \
-                     a.counts, m, a.geom, make_qarg<QK>(a))
-  if (a.q_kind < QK_GENERAL || a.q_kind > QK_STEREO_CV4) return hipErrorInvalidValue;
-  switch (ksize * 4 + a.q_kind) {
-    case 12: D2PC_CB_BS(3, QK_GENERAL); break;
-    case 13: D2PC_CB_BS(3, QK_STEREO); break;
-    case 14: D2PC_CB_BS(3, QK_STEREO_CV24); break;
-    case 15: D2PC_CB_BS(3, QK_STEREO_CV4); break;
-    case 20: D2PC_CB_BS(5, QK_GENERAL); break;
-    case 21: D2PC_CB_BS(5, QK_STEREO); break;
-    case 22: D2PC_CB_BS(5, QK_STEREO_CV24); break;
-    case 23: D2PC_CB_BS(5, QK_STEREO_CV4); break;
-    case 28: D2PC_CB_BS(7, QK_GENERAL); break;
-    case 29: D2PC_CB_BS(7, QK_STEREO); break;
-    case 30: D2PC_CB_BS(7, QK_STEREO_CV24); break;
-    case 31: D2PC_CB_BS(7, QK_STEREO_CV4); break;
-    case 36: D2PC_CB_BS(9, QK_GENERAL); break;
-    case 37: D2PC_CB_BS(9, QK_STEREO); break;
-    case 38: D2PC_CB_BS(9, QK_STEREO_CV24); break;
-    case 39: D2PC_CB_BS(9, QK_STEREO_CV4); break;
-    case 44: D2PC_CB_BS(11, QK_GENERAL); break;
-    case 45: D2PC_CB_BS(11, QK_STEREO); break;
-    case 46: D2PC_CB_BS(11, QK_STEREO_CV24); break;
-    case 47: D2PC_CB_BS(11, QK_STEREO_CV4); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef D2PC_CB_BS
-  return hipGetLastError();
+  return for_ksize(ksize, [&](auto ks) {
+    return for_q_kind(a.q_kind, [&](auto qk) {
+      constexpr int KS = decltype(ks)::value, QK = decltype(qk)::value;
+      hipLaunchKernelGGL((k_callback_bs<KS, QK>), dim3(uint32_t(blocks)), dim3(MedianBsShape<KS>::THREADS), D2PC_CB_LDS_PAD, a.stream, s8,
+                         o, a.out_index, a.counts, m, a.geom, make_qarg<QK>(a));
+      return hipGetLastError();
+    });
+  });
 }
 
 size_t callback_compact_state_bytes(uint32_t tiles_x, uint32_t tiles_y, uint32_t n_frames, uint32_t *frame_stride) {
@@ -879,16 +779,10 @@ size_t callback_compact_state_bytes(uint32_t tiles_x, uint32_t tiles_y, uint32_t
 }
 
 hipError_t launch_callback_bs_compact(const LaunchArgs &a, MedianArgs m, const void *src, int ksize) {
-  if (!median_ksize_supported(ksize) || m.out_w == 0 || m.out_h == 0 || !a.state || !a.stats || !a.counts) return hipErrorInvalidValue;
-  if (m.out_x0 != a.geom.border || m.out_y0 != a.geom.border || m.out_w != a.geom.roi_w ||
-      uint64_t(m.out_w) * m.out_h != a.geom.roi_n)
-    return hipErrorInvalidValue;  // the filter's output rectangle must be the reprojection's ROI
-  using S = MedianBsShape<11>;  // the tile shape does not depend on k
-  m.tiles_x = (m.out_w + S::TW - 1) / S::TW;
-  m.tiles_y = (m.out_h + S::TH - 1) / S::TH;
+  if (!a.state || !a.stats || !a.counts) return hipErrorInvalidValue;
+  uint64_t blocks = 0;
+  if (hipError_t e = cb_resolve_tiles(a, m, ksize, blocks); e != hipSuccess) return e;
   if (m.tiles_x > kCbMaxTilesX) return hipErrorInvalidValue;  // a band must fit the resident blocks (see the kernel)
-  const uint64_t blocks = uint64_t(m.tiles_x) * m.tiles_y * m.n_frames;
-  if (blocks == 0 || blocks > 0x7fffffffull) return hipErrorInvalidValue;
   uint32_t stride = 0;
   if (callback_compact_state_bytes(m.tiles_x, m.tiles_y, m.n_frames, &stride) != a.state_bytes || stride != a.geom.frame_state_stride ||
       a.geom.n_frames != m.n_frames)
@@ -902,41 +796,16 @@ hipError_t launch_callback_bs_compact(const LaunchArgs &a, MedianArgs m, const v
   if (pipe && (a.grid % m.n_frames != 0 || (a.grid / m.n_frames <= m.tiles_x && a.grid / m.n_frames < m.tiles_x * m.tiles_y)))
     return hipErrorInvalidValue;
   const uint32_t grid = pipe ? a.grid : uint32_t(blocks);
-#define D2PC_CB_BSC(KS, QK)                                                                                                  \
-  if (pipe)                                                                                                                  \
-    hipLaunchKernelGGL((k_callback_bs_compact_pipe<KS, QK>), dim3(grid), dim3(S::THREADS), 0, a.stream, s8, o, a.out_index,  \
-                       a.counts, state, m, a.geom, make_qarg<QK>(a));                                                       \
-  else                                                                                                                       \
-    hipLaunchKernelGGL((k_callback_bs_compact<KS, QK>), dim3(grid), dim3(S::THREADS), 0, a.stream, s8, o, a.out_index,      \
-                       a.counts, state, m, a.geom, make_qarg<QK>(a))
-  if (a.q_kind < QK_GENERAL || a.q_kind > QK_STEREO_CV4) return hipErrorInvalidValue;
-  switch (ksize * 4 + a.q_kind) {
-    case 12: D2PC_CB_BSC(3, QK_GENERAL); break;
-    case 13: D2PC_CB_BSC(3, QK_STEREO); break;
-    case 14: D2PC_CB_BSC(3, QK_STEREO_CV24); break;
-    case 15: D2PC_CB_BSC(3, QK_STEREO_CV4); break;
-    case 20: D2PC_CB_BSC(5, QK_GENERAL); break;
-    case 21: D2PC_CB_BSC(5, QK_STEREO); break;
-    case 22: D2PC_CB_BSC(5, QK_STEREO_CV24); break;
-    case 23: D2PC_CB_BSC(5, QK_STEREO_CV4); break;
-    case 28: D2PC_CB_BSC(7, QK_GENERAL); break;
-    case 29: D2PC_CB_BSC(7, QK_STEREO); break;
-    case 30: D2PC_CB_BSC(7, QK_STEREO_CV24); break;
-    case 31: D2PC_CB_BSC(7, QK_STEREO_CV4); break;
-    case 36: D2PC_CB_BSC(9, QK_GENERAL); break;
-    case 37: D2PC_CB_BSC(9, QK_STEREO); break;
-    case 38: D2PC_CB_BSC(9, QK_STEREO_CV24); break;
-    case 39: D2PC_CB_BSC(9, QK_STEREO_CV4); break;
-    case 44: D2PC_CB_BSC(11, QK_GENERAL); break;
-    case 45: D2PC_CB_BSC(11, QK_STEREO); break;
-    case 46: D2PC_CB_BSC(11, QK_STEREO_CV24); break;
-    case 47: D2PC_CB_BSC(11, QK_STEREO_CV4); break;
-    default: return hipErrorInvalidValue;
-  }
-#undef D2PC_CB_BSC
-  return hipGetLastError();
+  return for_ksize(ksize, [&](auto ks) {
+    return for_q_kind(a.q_kind, [&](auto qk) {
+      constexpr int KS = decltype(ks)::value, QK = decltype(qk)::value;
+      const auto kernel = pipe ? k_callback_bs_compact_pipe<KS, QK> : k_callback_bs_compact<KS, QK>;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(MedianBsShape<KS>::THREADS), 0, a.stream, s8, o, a.out_index, a.counts, state, m, a.geom,
+                         make_qarg<QK>(a));
+      return hipGetLastError();
+    });
+  });
 }
-
 
 }  // namespace d2pc
 

@@ -84,6 +84,18 @@ __device__ __forceinline__ void backoff(uint32_t spins) {
   for (uint32_t j = 0; j < n; ++j) __builtin_amdgcn_s_sleep(1);
 }
 
+// Should a wave that has waited since w0 give up?  Waits are bounded by time: the budget is spent, or ANY wave of the launch
+// has given up already (sticky flag), so a broken launch drains at once instead of timing out tile by tile.  The launch's
+// first give-up counts it (d2pc_compact_stats).  How often a wait asks is its own business.
+__device__ __forceinline__ bool wait_gave_up(StateHeader *hdr, uint32_t lane, uint64_t w0, uint32_t spin_ticks) {
+  if (!(__builtin_amdgcn_s_memrealtime() - w0 > uint64_t(spin_ticks) ||
+        __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
+    return false;
+  if (lane == 0 && __hip_atomic_exchange(&hdr->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+    atomicAdd(&hdr->stats->timeouts, 1ull);
+  return true;
+}
+
 // What a control wave's waits cost, summed over the block's tiles.  The sums live in LDS (three words of the
 // block), not in registers: the single pass has no scalar register to spare -- kept in registers, these two
 // counters cost 9 % (16 x 4K) to 25 % (32 x 1080p) of the kernel's time through the spills they caused in the
@@ -117,16 +129,8 @@ __device__ __forceinline__ uint64_t read_counted(const uint64_t *p, bool on, Sta
         v = __hip_atomic_load((gu64 *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ok = ready(v);
       }
-      // bounded by time: give up once the budget is spent, and as soon as ANY wave of the launch has
-      // given up (sticky flag), so a broken launch drains at once instead of timing out tile by tile
       ++spins;
-      if ((spins & 15u) == 0 &&
-          (__builtin_amdgcn_s_memrealtime() - t0 > uint64_t(spin_ticks) ||
-           __hip_atomic_load(&hdr->timeout, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-        if (lane == 0 && __hip_atomic_exchange(&hdr->timeout, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
-          atomicAdd(&hdr->stats->timeouts, 1ull);  // the launch's first give-up counts it (d2pc_compact_stats)
-        break;
-      }
+      if ((spins & 15u) == 0 && wait_gave_up(hdr, lane, t0, spin_ticks)) break;
     }
 #if D2PC_ONEPASS_STATS
     if (spins && lane == 0) {  // production counters (d2pc_compact_stats): failed polls and the time they took

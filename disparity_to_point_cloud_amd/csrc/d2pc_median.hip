@@ -27,6 +27,7 @@
 
 #include "d2pc_launch.hpp"
 #include "d2pc_median_tile.hpp"
+#include "d2pc_pixel.hpp"
 
 namespace d2pc {
 
@@ -150,14 +151,7 @@ hipError_t launch_median(const void *src, void *dst, const MedianArgs &args, int
   }
   if (a.out_x0 + a.out_w > a.width || a.out_y0 + a.out_h > a.height) return hipErrorInvalidValue;
   if (median_uses_bs(a, ksize)) return launch_median_bs(src, dst, a, ksize, stream);
-  switch (ksize) {
-    case 3: return launch_k<3>(s, d, a, stream);
-    case 5: return launch_k<5>(s, d, a, stream);
-    case 7: return launch_k<7>(s, d, a, stream);
-    case 9: return launch_k<9>(s, d, a, stream);
-    case 11: return launch_k<11>(s, d, a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return for_ksize(ksize, [&](auto ks) { return launch_k<decltype(ks)::value>(s, d, a, stream); });
 }
 
 }  // namespace d2pc

@@ -2,6 +2,7 @@
 // d2pc_median_bs_tile.hpp); second device form of cv::medianBlur(img, out, 11) at reference
 // src/disparity_to_point_cloud.cpp:55-57.
 #include "d2pc_median_bs_tile.hpp"
+#include "d2pc_pixel.hpp"
 
 namespace d2pc {
 
@@ -97,14 +98,7 @@ uint64_t median_bs_tiles(const MedianArgs &a) {
 hipError_t launch_median_bs(const void *src, void *dst, const MedianArgs &a, int ksize, hipStream_t stream) {
   const uint8_t *s = static_cast<const uint8_t *>(src);
   uint8_t *d = static_cast<uint8_t *>(dst);
-  switch (ksize) {
-    case 3: return launch_bs<3>(s, d, a, stream);
-    case 5: return launch_bs<5>(s, d, a, stream);
-    case 7: return launch_bs<7>(s, d, a, stream);
-    case 9: return launch_bs<9>(s, d, a, stream);
-    case 11: return launch_bs<11>(s, d, a, stream);
-    default: return hipErrorInvalidValue;
-  }
+  return for_ksize(ksize, [&](auto ks) { return launch_bs<decltype(ks)::value>(s, d, a, stream); });
 }
 
 }  // namespace d2pc

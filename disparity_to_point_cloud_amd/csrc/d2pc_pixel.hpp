@@ -494,6 +494,18 @@ inline hipError_t for_dtype(int dtype, F &&f) {
   }
   return hipErrorInvalidValue;
 }
+// f(std::integral_constant<int, KS>{}) for the median's window (median_ksize_supported)
+template <class F>
+inline hipError_t for_ksize(int ksize, F &&f) {
+  switch (ksize) {
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    case 9: return f(std::integral_constant<int, 9>{});
+    case 11: return f(std::integral_constant<int, 11>{});
+  }
+  return hipErrorInvalidValue;
+}
 // f(dtype constant, std::bool_constant<VEC>{}): 16-byte row loads exist for fp32 rows only
 template <class F>
 inline hipError_t for_dtype_vec(const LaunchArgs &a, F &&f) {

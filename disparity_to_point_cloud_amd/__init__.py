@@ -66,6 +66,13 @@ from .capi import (  # noqa: F401
     NODE_MATCHING_SCORE_1,
     NODE_MATCHING_SCORE_2,
     NODE_TOPICS,
+    RIG_MAX_CAMERAS,
+    RigConfig,
+    RigGeometry,
+    RigSession,
+    rig_compose_q,
+    rig_config_init,
+    rig_geometry,
 )
 
 

@@ -34,6 +34,8 @@ ABI_SYMBOLS = [
     "d2pc_score_filter_device", "d2pc_colorize_table", "d2pc_colorize_desc_init", "d2pc_colorize_device",
     "d2pc_fusion_node_config_init", "d2pc_fusion_node_geometry", "d2pc_fusion_node_create", "d2pc_fusion_node_destroy",
     "d2pc_fusion_node_callback_device", "d2pc_fusion_node_callback",
+    "d2pc_rig_config_init", "d2pc_rig_geometry", "d2pc_rig_compose_q", "d2pc_rig_create", "d2pc_rig_set_q",
+    "d2pc_rig_get_q", "d2pc_rig_process_device", "d2pc_rig_destroy",
 ]
 # include/d2pc_ext.h: unstable, for bench.py / tools / tests only
 EXT_SYMBOLS = [
@@ -49,6 +51,7 @@ FORM_DEFAULT, FORM_CV24, FORM_CV4 = 0, 24, 4   # d2pc_reproject_form
 SCORE_FORM_CV4, SCORE_FORM_CV3 = 4, 3  # d2pc_score_form
 NODE_DISPARITY_1, NODE_DISPARITY_2, NODE_MATCHING_SCORE_1, NODE_MATCHING_SCORE_2 = range(4)  # d2pc_fusion_node_callback_id
 # d2pc_fusion_node_topic_id, in the order of the reference's publishers
+RIG_MAX_CAMERAS = 64
 NODE_TOPICS = ("cropped_depth_1", "cropped_depth_2", "cropped_score_1", "cropped_score_2", "fused_depth_map",
                "combined_score", "gradient")
 
@@ -154,6 +157,16 @@ class FusionNodeHostTopics(ctypes.Structure):
         ("capacity", ctypes.c_size_t * 7), ("bytes", ctypes.c_size_t * 7), ("width", ctypes.c_int32 * 7),
         ("height", ctypes.c_int32 * 7), ("channels", ctypes.c_int32 * 7),
     ]
+
+
+class RigConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_cameras", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("height", ctypes.c_int32), ("dtype", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class RigGeometry(ctypes.Structure):
+    _fields_ = [("roi_points", ctypes.c_size_t), ("capacity_points", ctypes.c_size_t), ("device_bytes", ctypes.c_size_t),
+                ("index_available", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
 
 
 class StageTimes(ctypes.Structure):
@@ -321,6 +334,16 @@ def load_library(variant=None):
     L.d2pc_fusion_node_callback_device.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.c_size_t,
                                                    ctypes.POINTER(FusionNodeTopics), vp]
     L.d2pc_fusion_node_callback.argtypes = [vp, ctypes.c_int, vp, ctypes.c_size_t, ctypes.POINTER(FusionNodeHostTopics)]
+    L.d2pc_rig_config_init.argtypes = [ctypes.POINTER(RigConfig)]
+    L.d2pc_rig_config_init.restype = None
+    L.d2pc_rig_geometry.argtypes = [ctypes.POINTER(RigConfig), ctypes.c_int, ctypes.POINTER(RigGeometry)]
+    L.d2pc_rig_compose_q.argtypes = [dp, dp, dp]
+    L.d2pc_rig_create.argtypes = [vp, ctypes.POINTER(RigConfig), dp, ctypes.POINTER(vp)]
+    L.d2pc_rig_set_q.argtypes = [vp, ctypes.c_int, dp]
+    L.d2pc_rig_get_q.argtypes = [vp, ctypes.c_int, dp]
+    L.d2pc_rig_process_device.argtypes = [vp, vp, ctypes.c_float, ctypes.c_size_t, ctypes.c_size_t, vp, vp, ctypes.c_size_t,
+                                          vp, vp, vp]
+    L.d2pc_rig_destroy.argtypes = [vp]
     L.d2pc_crop_to_square.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 3
     L.d2pc_check_async_error.argtypes = [vp]
     L.d2pc_reserve_mono.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -774,6 +797,99 @@ def fusion_node_geometry(cfg: FusionNodeConfig) -> FusionNodeGeometry:
     if st != 0:
         raise D2pcError(st, "fusion_node_geometry(%dx%d, %d/%d)" % (cfg.cols, cfg.rows, cfg.offset_x, cfg.offset_y))
     return g
+
+
+def rig_config_init(**kw) -> RigConfig:
+    """d2pc_rig_config_init, then the given fields."""
+    c = RigConfig()
+    load_library().d2pc_rig_config_init(ctypes.byref(c))
+    for k, v in kw.items():
+        if k not in dict(RigConfig._fields_):
+            raise TypeError("d2pc_rig_config has no field %r" % k)
+        setattr(c, k, v)
+    return c
+
+
+def rig_geometry(cfg: RigConfig, border: int) -> RigGeometry:
+    """d2pc_rig_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = RigGeometry()
+    st = load_library().d2pc_rig_geometry(ctypes.byref(cfg), border, ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "rig_geometry(%d x %dx%d, border %d)" % (cfg.n_cameras, cfg.width, cfg.height, border))
+    return g
+
+
+def rig_compose_q(t, q) -> np.ndarray:
+    """d2pc_rig_compose_q: T.Q in the library's fixed association (a pose folded into a camera's Q); (4, 4) float64."""
+    t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(16))
+    q = np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(16))
+    out = np.zeros(16, dtype=np.float64)
+    as_dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))  # noqa: E731
+    st = load_library().d2pc_rig_compose_q(as_dp(t), as_dp(q), as_dp(out))
+    if st != 0:
+        raise D2pcError(st, "rig_compose_q")
+    return out.reshape(4, 4)
+
+
+class RigSession:
+    """d2pc_rig_*: n cameras of one geometry and dtype, one Q each, one merged cloud per call.  Border, mode,
+    min_disparity and the reproject form are the context's, read at every call."""
+
+    def __init__(self, ctx: "Context", n_cameras, width, height, dtype, qs):
+        self._L, self.ctx, self._h = ctx._L, ctx, None
+        self.cfg = rig_config_init(n_cameras=n_cameras, width=width, height=height, dtype=dtype)
+        qs = np.ascontiguousarray(np.asarray(qs, dtype=np.float64).reshape(-1))
+        if qs.size != 16 * int(n_cameras):
+            raise ValueError("qs must hold n_cameras x 16 doubles")
+        h = ctypes.c_void_p()
+        st = self._L.d2pc_rig_create(ctx.handle, ctypes.byref(self.cfg), qs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                     ctypes.byref(h))
+        if st:
+            raise D2pcError(st, self._L.d2pc_last_error(ctx.handle).decode())
+        self._h = h
+        self.n_cameras, self.width, self.height, self.dtype = int(n_cameras), int(width), int(height), int(dtype)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.d2pc_rig_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _check(self, st):
+        if st:
+            raise D2pcError(st, self._L.d2pc_last_error(self.ctx.handle).decode())
+
+    def geometry(self) -> RigGeometry:
+        """For the context's border as it is now."""
+        return rig_geometry(self.cfg, self.ctx.config().border)
+
+    def set_q(self, camera: int, q):
+        q = np.ascontiguousarray(np.asarray(q, dtype=np.float64).reshape(16))
+        self._check(self._L.d2pc_rig_set_q(self._h, camera, q.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+
+    def get_q(self, camera: int) -> np.ndarray:
+        q = np.zeros(16, dtype=np.float64)
+        st = self._L.d2pc_rig_get_q(self._h, camera, q.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+        if st:
+            raise D2pcError(st, "rig_get_q(%d)" % camera)
+        return q
+
+    def process_device(self, d_frames_ptr, scale, row_stride, frame_stride, d_out_ptr, d_index_ptr, capacity_points,
+                       d_counts_ptr, d_offsets_ptr, stream_ptr=None):
+        """d2pc_rig_process_device on raw pointers."""
+        self._check(self._L.d2pc_rig_process_device(self._h, d_frames_ptr, scale, row_stride, frame_stride, d_out_ptr,
+                                                    d_index_ptr, capacity_points, d_counts_ptr, d_offsets_ptr, stream_ptr))
 
 
 def _frame_shape(rows, cols, batch):

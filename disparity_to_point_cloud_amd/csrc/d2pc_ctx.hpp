@@ -8,6 +8,7 @@
 //   d2pc_capi_mono.hip     cv_bridge rescale, median, the device-resident callback body (d2pc_process_mono_device)
 //   d2pc_capi_fusion.hip   depth-map fusion inner loop, rotate, crop
 //   d2pc_capi_node.hip     the depth_map_fusion node as a session (d2pc_fusion_node_*)
+//   d2pc_capi_rig.hip      a camera rig as a session (d2pc_rig_*: n cameras, n Qs in a device table, one merged cloud; d2pc_rig.hpp)
 //   d2pc_capi_ext.hip      include/d2pc_ext.h: tuning keys, test hooks, device calibration kernels
 //   d2pc_plane.hpp         one image plane (pointer, pitch, frame stride, rows x row bytes): fit, extent, overlap; no HIP.
 //                          Which rule each image entry point passes to Plane::fits (d2pc_process* have make_geom's own):
@@ -16,6 +17,7 @@
 //     d2pc_mono16_to_mono8_device                        Bound32::Pitch, FrameRule::LastRow; pitch, frame stride, base even
 //     d2pc_median_device, d2pc_median_roi_device         Bound32::Pitch, FrameRule::WholeRows (rows * pitch); no overlap test
 //     d2pc_fusion_node_callback_device (incoming frame)  Bound32::Pitch, FrameRule::LastRow
+//     d2pc_rig_process_device (the cameras' frames)      Bound32::Plane, FrameRule::LastRow, behind make_geom's own rules
 // Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol).
 #pragma once
 #include <hip/hip_runtime.h>

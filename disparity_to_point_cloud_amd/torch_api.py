@@ -52,6 +52,41 @@ class DeviceBatch:
         return out
 
 
+class RigBatch:
+    """Pre-allocated device buffers for a camera rig: n cameras of one size and dtype, one Q each (`qs`: n x 16), ONE
+    merged cloud per launch (capi.RigSession).  The buffers are sized for the context's border at construction."""
+
+    def __init__(self, ctx: capi.Context, qs, height: int, width: int, dtype=torch.float32, want_index=False,
+                 device="cuda:0"):
+        qs = np.asarray(qs, dtype=np.float64).reshape(-1, 16)
+        self.ctx, self.n_cameras, self.height, self.width = ctx, len(qs), height, width
+        self.rig = capi.RigSession(ctx, self.n_cameras, width, height, _T2DT[dtype], qs)
+        self.capacity = int(self.rig.geometry().capacity_points)
+        self.device = torch.device(device)
+        self.frames = torch.empty((self.n_cameras, height, width), dtype=dtype, device=self.device)
+        self.points = torch.empty((max(self.capacity, 1), 4), dtype=torch.float32, device=self.device)
+        self.index = torch.empty((max(self.capacity, 1),), dtype=torch.int32, device=self.device) if want_index else None
+        self.counts = torch.zeros((self.n_cameras,), dtype=torch.int32, device=self.device)
+        self.offsets = torch.zeros((self.n_cameras + 1,), dtype=torch.int32, device=self.device)
+
+    def launch(self, scale=1.0, stream=None):
+        """Enqueue one call over the rig's frames on `stream` (default: torch's current stream).  Asynchronous."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        d = self.frames
+        self.rig.process_device(d.data_ptr(), scale, d.stride(1) * d.element_size(), d.stride(0) * d.element_size(),
+                                self.points.data_ptr(), self.index.data_ptr() if self.index is not None else None,
+                                self.capacity, self.counts.data_ptr(), self.offsets.data_ptr(), s.cuda_stream)
+
+    def results(self):
+        """Synchronise and copy back: (points, index or None, counts, offsets) of the merged cloud."""
+        torch.cuda.synchronize(self.device)
+        offsets = self.offsets.cpu().numpy().view(np.uint32).astype(np.int64)
+        counts = self.counts.cpu().numpy().view(np.uint32).astype(np.int64)
+        n = int(offsets[-1])
+        idx = self.index[:n].cpu().numpy().view(np.uint32) if self.index is not None else None
+        return self.points[:n].cpu().numpy(), idx, counts, offsets
+
+
 def fuse_planes(ctx: capi.Context, planes, rule=capi.FUSE_GRAD_FILTER, crop=(0, 40, 30, 10), want_combined=True,
                 stream=None):
     """d2pc_fuse_device on torch uint8 CUDA tensors.

@@ -655,6 +655,73 @@ typedef struct d2pc_fusion_node_host_topics {
 int d2pc_fusion_node_callback(d2pc_fusion_node *node, int which, const void *host_frame, size_t pitch,
                               d2pc_fusion_node_host_topics *io);
 
+/*
+ * A camera RIG as a session: n cameras of one geometry and sample type, each with its OWN Q, turned into ONE cloud by
+ * one asynchronous call.  The reference is deployed on such a rig (hpp:71 "Omni-stereo"; its cloud topic is the merged
+ * /omi_cam/point_cloud), and a batch of frames arises from n cameras at one instant, not from one camera n times.
+ * A camera's pose is folded into its Q: [X Y Z W] = Q.(u,v,d,1), so a rigid T in front of Q is just another Q
+ * (d2pc_rig_compose_q) and cv::reprojectImageTo3D's arithmetic stays the specification.
+ *
+ * Border, mode, min_disparity and the reproject form are the CONTEXT's, read at every d2pc_rig_process_device call:
+ *   PARITY   camera f's (W-2b)(H-2b) points at point f * roi_points, reference order inside each camera
+ *   COMPACT  the survivors of camera 0, then of camera 1, ...: dense, row-major inside each camera; the per-camera
+ *            counts and start offsets are written on the device and the host never reads a count
+ * The per-camera calibrations live in a table in device memory; a camera whose Q has cv::stereoRectify's structure
+ * takes the specialised arithmetic, any other (a posed camera) the general one, exactly as d2pc_process_device
+ * would with d2pc_set_q(that Q): same bytes.  D2PC_FORM_CV24 is refused (D2PC_ERR_INVALID_ARG): its per-row segments
+ * are host work per Q and per width.
+ */
+#define D2PC_RIG_MAX_CAMERAS 64
+typedef struct d2pc_rig_config {
+  uint32_t struct_size;        /* sizeof(d2pc_rig_config) */
+  int32_t n_cameras;           /* 1 .. D2PC_RIG_MAX_CAMERAS */
+  int32_t width, height;       /* of every camera's frame */
+  int32_t dtype;               /* D2PC_DTYPE_F32 / _U8 / _U16 */
+  int32_t reserved[3];
+} d2pc_rig_config;
+/* struct_size, one camera, D2PC_DTYPE_F32; width = height = 0: the caller's to set. */
+void d2pc_rig_config_init(d2pc_rig_config *cfg);
+
+typedef struct d2pc_rig_geometry_t {
+  size_t roi_points;           /* ROI points of one camera: d2pc_roi_points(width, height, border) */
+  size_t capacity_points;      /* n_cameras * roi_points: what d_out_points (and d_out_index) must hold */
+  size_t device_bytes;         /* device memory the session holds (calibration table + tile counts) */
+  int32_t index_available;     /* 0 when n_cameras * width * height > 2^32: d_out_index is refused */
+  int32_t reserved[3];
+} d2pc_rig_geometry_t;
+/* Host arithmetic only (no context, no device); the refusals are d2pc_rig_create's: D2PC_ERR_INVALID_ARG (NULL,
+ * struct_size, n_cameras, border), D2PC_ERR_BAD_DTYPE, D2PC_ERR_BAD_SIZE (width or height <= 0, a frame beyond 2^31
+ * pixels or a ROI beyond 2^28, n_cameras * roi_points >= 2^32).  A border wider than the frame gives 0 points. */
+int d2pc_rig_geometry(const d2pc_rig_config *cfg, int border, d2pc_rig_geometry_t *out);
+
+/* out = T.Q, row-major 4 x 4, host only: out[r][k] = ((t_r0*q_0k + t_r1*q_1k) + t_r2*q_2k) + t_r3*q_3k, every product
+ * and sum rounded on its own (no fused multiply-add).  T need not be rigid; non-finite entries are refused
+ * (D2PC_ERR_INVALID_ARG).  `out` may be `t` or `q`.  The identity leaves a stereoRectify Q with that structure. */
+int d2pc_rig_compose_q(const double t[16], const double q[16], double out[16]);
+
+typedef struct d2pc_rig d2pc_rig;
+/* q: n_cameras x 16 doubles, camera after camera.  Allocates everything the session will ever need (sized for border
+ * 0): d2pc_rig_process_device allocates nothing and can be captured into a graph in both modes without a warm-up.
+ * The rig lives on `ctx`'s device and must be destroyed before the context. */
+int d2pc_rig_create(d2pc_ctx *ctx, const d2pc_rig_config *cfg, const double *q, d2pc_rig **out);
+/* Synchronous; the caller has no launch of this rig in flight.  A captured graph reads the table when it REPLAYS:
+ * a replay after d2pc_rig_set_q uses the new Q. */
+int d2pc_rig_set_q(d2pc_rig *rig, int camera, const double q[16]);
+int d2pc_rig_get_q(const d2pc_rig *rig, int camera, double q_out[16]);
+/*
+ * The n resident frames (camera f at d_frames + f * frame_stride_bytes, rows row_stride_bytes apart; `scale` as in
+ * d2pc_process_device) into one cloud at d_out_points (16-byte aligned), asynchronous on `stream` (NULL = the HIP
+ * default stream).  capacity_points < n_cameras * roi_points gives D2PC_ERR_CAPACITY before anything is enqueued.
+ * d_out_index (nullable) receives f * width * height + v * width + u, the pixel's index in the batch.
+ * d_counts (n) and d_offsets (n + 1; d_offsets[n] = the cloud's points) are nullable in PARITY and required in
+ * COMPACT.  The frames must not overlap the outputs.  The tile counts belong to the rig: one launch of a rig in
+ * flight per stream order; two streams need two rigs.
+ */
+int d2pc_rig_process_device(d2pc_rig *rig, const void *d_frames, float scale, size_t row_stride_bytes,
+                            size_t frame_stride_bytes, void *d_out_points, uint32_t *d_out_index,
+                            size_t capacity_points, uint32_t *d_counts, uint32_t *d_offsets, void *stream);
+int d2pc_rig_destroy(d2pc_rig *rig);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,18 @@ from .capi import (  # noqa: F401
     rig_compose_q,
     rig_config_init,
     rig_geometry,
+    POINT_XYZI,
+    POINT_XYZRGB,
+    TEX_U8,
+    TEX_U16,
+    TEX_F32,
+    TEX_RGB8,
+    TEX_BGR8,
+    TEX_MONO8,
+    TextureDesc,
+    TexturedCloudMeta,
+    texture_desc_init,
+    textured_cloud_meta,
 )
 
 

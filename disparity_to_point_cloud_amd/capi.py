@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "d2pc_fusion_node_callback_device", "d2pc_fusion_node_callback",
     "d2pc_rig_config_init", "d2pc_rig_geometry", "d2pc_rig_compose_q", "d2pc_rig_create", "d2pc_rig_set_q",
     "d2pc_rig_get_q", "d2pc_rig_process_device", "d2pc_rig_destroy",
+    "d2pc_texture_desc_init", "d2pc_texture_device", "d2pc_textured_cloud_meta_fill",
 ]
 # include/d2pc_ext.h: unstable, for bench.py / tools / tests only
 EXT_SYMBOLS = [
@@ -52,6 +53,8 @@ SCORE_FORM_CV4, SCORE_FORM_CV3 = 4, 3  # d2pc_score_form
 NODE_DISPARITY_1, NODE_DISPARITY_2, NODE_MATCHING_SCORE_1, NODE_MATCHING_SCORE_2 = range(4)  # d2pc_fusion_node_callback_id
 # d2pc_fusion_node_topic_id, in the order of the reference's publishers
 RIG_MAX_CAMERAS = 64
+POINT_XYZI, POINT_XYZRGB = 1, 2  # d2pc_point_format
+TEX_U8, TEX_U16, TEX_F32, TEX_RGB8, TEX_BGR8, TEX_MONO8 = range(1, 7)  # d2pc_texture_format
 NODE_TOPICS = ("cropped_depth_1", "cropped_depth_2", "cropped_score_1", "cropped_score_2", "fused_depth_map",
                "combined_score", "gradient")
 
@@ -167,6 +170,31 @@ class RigConfig(ctypes.Structure):
 class RigGeometry(ctypes.Structure):
     _fields_ = [("roi_points", ctypes.c_size_t), ("capacity_points", ctypes.c_size_t), ("device_bytes", ctypes.c_size_t),
                 ("index_available", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+
+class TextureDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("point_format", ctypes.c_int32), ("texture_format", ctypes.c_int32),
+        ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("border", ctypes.c_int32), ("n_frames", ctypes.c_int32),
+        ("merged", ctypes.c_int32),
+        ("texture", ctypes.c_void_p), ("tex_pitch", ctypes.c_size_t), ("tex_frame_stride", ctypes.c_size_t),
+        ("points", ctypes.c_void_p), ("index", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+        ("cloud_points", ctypes.c_size_t), ("points_frame_stride_points", ctypes.c_size_t),
+        ("out", ctypes.c_void_p), ("out_frame_stride_points", ctypes.c_size_t),
+    ]
+
+
+class TexturedField(ctypes.Structure):
+    _fields_ = [("name", ctypes.c_char * 12), ("offset", ctypes.c_uint32), ("datatype", ctypes.c_uint8),
+                ("count", ctypes.c_uint32)]
+
+
+class TexturedCloudMeta(ctypes.Structure):
+    _fields_ = [
+        ("height", ctypes.c_uint32), ("width", ctypes.c_uint32), ("point_step", ctypes.c_uint32),
+        ("row_step", ctypes.c_uint32), ("is_bigendian", ctypes.c_uint8), ("is_dense", ctypes.c_uint8),
+        ("n_fields", ctypes.c_uint32), ("fields", TexturedField * 4),
+    ]
 
 
 class StageTimes(ctypes.Structure):
@@ -344,6 +372,11 @@ def load_library(variant=None):
     L.d2pc_rig_process_device.argtypes = [vp, vp, ctypes.c_float, ctypes.c_size_t, ctypes.c_size_t, vp, vp, ctypes.c_size_t,
                                           vp, vp, vp]
     L.d2pc_rig_destroy.argtypes = [vp]
+    L.d2pc_texture_desc_init.argtypes = [ctypes.POINTER(TextureDesc)]
+    L.d2pc_texture_desc_init.restype = None
+    L.d2pc_texture_device.argtypes = [vp, ctypes.POINTER(TextureDesc), vp]
+    L.d2pc_textured_cloud_meta_fill.argtypes = [ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
+                                                ctypes.POINTER(TexturedCloudMeta)]
     L.d2pc_crop_to_square.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)] * 3
     L.d2pc_check_async_error.argtypes = [vp]
     L.d2pc_reserve_mono.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -679,6 +712,10 @@ class Context:
         """d2pc_colorize_device: the view of DisparityCb1/2 (optionally of the rotated frame) and its colorizeDepth."""
         self._check(self._L.d2pc_colorize_device(self._h, ctypes.byref(desc), stream_ptr))
 
+    def texture_device(self, desc: "TextureDesc", stream_ptr=None):
+        """d2pc_texture_device: a producer's points + a per-pixel plane -> 32-byte PointXYZI / PointXYZRGB records."""
+        self._check(self._L.d2pc_texture_device(self._h, ctypes.byref(desc), stream_ptr))
+
     def rotate_cw_device(self, d_src_ptr, cols, rows, src_pitch, src_frame_stride, n_frames, d_dst_ptr, dst_pitch,
                          dst_frame_stride, stream_ptr=None):
         """d2pc_rotate_cw_device: dst(i, j) = src(rows-1-j, i) for 8-bit device frames."""
@@ -756,6 +793,26 @@ def colorize_desc_init() -> ColorizeDesc:
     d = ColorizeDesc()
     load_library().d2pc_colorize_desc_init(ctypes.byref(d))
     return d
+
+
+def texture_desc_init(**kw) -> TextureDesc:
+    """d2pc_texture_desc_init, then the given fields."""
+    d = TextureDesc()
+    load_library().d2pc_texture_desc_init(ctypes.byref(d))
+    for k, v in kw.items():
+        if k not in dict(TextureDesc._fields_):
+            raise TypeError("d2pc_texture_desc has no field %r" % k)
+        setattr(d, k, v)
+    return d
+
+
+def textured_cloud_meta(point_format: int, n_points: int, is_dense: bool) -> TexturedCloudMeta:
+    """d2pc_textured_cloud_meta_fill (host only); raises D2pcError as the C function refuses."""
+    m = TexturedCloudMeta()
+    st = load_library().d2pc_textured_cloud_meta_fill(point_format, n_points, int(bool(is_dense)), ctypes.byref(m))
+    if st != 0:
+        raise D2pcError(st, "textured_cloud_meta(%d, %d)" % (point_format, n_points))
+    return m
 
 
 def colorize_table() -> np.ndarray:

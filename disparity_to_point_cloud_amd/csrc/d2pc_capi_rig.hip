@@ -2,6 +2,7 @@
 // in as T.Q), one merged cloud per call.  The per-camera calibrations live in a device table the kernels of d2pc_rig.hip
 // read; the tile counts of the COMPACT form are the rig's own, allocated once for border 0.  Planes are checked through
 // d2pc_plane.hpp: the frames with Bound32::Plane (the kernels form a row's offset in 32 bits), FrameRule::LastRow.
+// At the end: the textured clouds (d2pc_texture_*), which need no session -- here for the product library's size budget.
 #include "d2pc_ctx.hpp"
 #include "d2pc_rig.hpp"
 
@@ -215,6 +216,113 @@ int d2pc_rig_process_device(d2pc_rig *rig, const void *d_frames, float scale, si
   a.frame_pixels = uint32_t(uint64_t(c.width) * uint64_t(c.height));
   a.stream = s;
   D2PC_HIP(ctx, compact ? launch_rig_compact(a) : launch_rig_parity(a));
+  return D2PC_OK;
+}
+
+// ---- textured clouds (d2pc_texture_*): lives here to share this translation unit and the rig's code object ----------
+void d2pc_texture_desc_init(d2pc_texture_desc *desc) {
+  if (!desc) return;
+  memset(desc, 0, sizeof *desc);
+  desc->struct_size = sizeof *desc;
+  desc->point_format = D2PC_POINT_XYZI;
+  desc->texture_format = D2PC_TEX_U8;
+  desc->n_frames = 1;
+}
+
+int d2pc_textured_cloud_meta_fill(int point_format, size_t n, int is_dense, d2pc_textured_cloud_meta *m) {
+  if (!m) return D2PC_ERR_INVALID_ARG;
+  if (point_format != D2PC_POINT_XYZI && point_format != D2PC_POINT_XYZRGB) return D2PC_ERR_BAD_DTYPE;
+  if (n > 0xffffffffull / 32) return D2PC_ERR_BAD_SIZE;
+  memset(m, 0, sizeof *m);
+  m->height = 1;
+  m->width = uint32_t(n);
+  m->point_step = 32;
+  m->row_step = uint32_t(32 * n);
+  m->is_dense = is_dense ? 1 : 0;
+  m->n_fields = 4;
+  const char *names[4] = {"x", "y", "z", point_format == D2PC_POINT_XYZI ? "intensity" : "rgb"};
+  for (int i = 0; i < 4; ++i) {
+    strncpy(m->fields[i].name, names[i], sizeof m->fields[i].name - 1);
+    m->fields[i].offset = i < 3 ? uint32_t(4 * i) : 16u;
+    m->fields[i].datatype = 7;  // sensor_msgs::PointField::FLOAT32
+    m->fields[i].count = 1;
+  }
+  return D2PC_OK;
+}
+
+int d2pc_texture_device(d2pc_ctx *ctx, const d2pc_texture_desc *d, void *stream) {
+  if (!ctx) return D2PC_ERR_INVALID_ARG;
+  if (!d || d->struct_size != sizeof(d2pc_texture_desc)) return fail(ctx, D2PC_ERR_INVALID_ARG, "bad d2pc_texture_desc");
+  if (!d->texture || !d->points || !d->out) return fail(ctx, D2PC_ERR_INVALID_ARG, "null device pointer");
+  TexArgs a;
+  size_t bpp = 1;
+  switch (d->texture_format) {
+    case D2PC_TEX_U8: a.kind = TEX_U8; break;
+    case D2PC_TEX_U16: a.kind = TEX_U16, bpp = 2; break;
+    case D2PC_TEX_F32: a.kind = TEX_F32, bpp = 4; break;
+    case D2PC_TEX_RGB8: a.kind = TEX_RGB8, bpp = 3; break;
+    case D2PC_TEX_BGR8: a.kind = TEX_BGR8, bpp = 3; break;
+    case D2PC_TEX_MONO8: a.kind = TEX_MONO8; break;
+    default: return fail(ctx, D2PC_ERR_BAD_DTYPE, "unknown texture format %d", d->texture_format);
+  }
+  const bool rgb = a.kind >= TEX_RGB8;
+  if (d->point_format != (rgb ? D2PC_POINT_XYZRGB : D2PC_POINT_XYZI))
+    return fail(ctx, D2PC_ERR_BAD_DTYPE, "texture format %d does not belong to point format %d", d->texture_format, d->point_format);
+  if (d->width <= 0 || d->height <= 0 || d->n_frames <= 0 || d->n_frames > 65535 || d->border < 0)
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "%d frames of %dx%d, border %d", d->n_frames, d->width, d->height, d->border);
+  const uint64_t frame_pixels = uint64_t(d->width) * uint64_t(d->height);
+  const bool merged = d->merged != 0;
+  if (frame_pixels > (uint64_t(1) << 31) || (merged && frame_pixels * uint64_t(d->n_frames) > (uint64_t(1) << 32)))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "%d frames of %dx%d: a pixel index does not fit 32 bits", d->n_frames, d->width, d->height);
+  if (d->cloud_points == 0 || uint64_t(d->cloud_points) >= (uint64_t(1) << 32))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "cloud_points of %zu: a point's position is 32 bits", d->cloud_points);
+  if (!d->index) {
+    if (merged) return fail(ctx, D2PC_ERR_INVALID_ARG, "a merged cloud needs its index");
+    if (d->cloud_points != d2pc_roi_points(d->width, d->height, d->border))
+      return fail(ctx, D2PC_ERR_BAD_SIZE, "no index: cloud_points must be the %zu ROI points", d2pc_roi_points(d->width, d->height, d->border));
+  }
+  const int n_clouds = merged ? 1 : d->n_frames;
+  const size_t cp = d->cloud_points;
+  if (n_clouds > 1 && (d->points_frame_stride_points < cp || d->out_frame_stride_points < cp))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "a frame stride is smaller than cloud_points (%zu)", cp);
+  // 65,535 clouds x 2^40 records x 32 B and 65,535 planes x 2^46 B stay below 2^62: no hull below can wrap
+  constexpr size_t kMaxStride = size_t(1) << 40, kMaxTexStride = size_t(1) << 46;
+  if (n_clouds > 1 && (d->points_frame_stride_points > kMaxStride || d->out_frame_stride_points > kMaxStride))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "a frame stride beyond 2^40 points");
+  if (d->n_frames > 1 && d->tex_frame_stride > kMaxTexStride) return fail(ctx, D2PC_ERR_BAD_SIZE, "tex_frame_stride beyond 2^46 bytes");
+  auto misaligned = [](const void *p, size_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; };
+  if (misaligned(d->points, 16) || misaligned(d->out, 16)) return fail(ctx, D2PC_ERR_INVALID_ARG, "points and out must be 16-byte aligned");
+  if (misaligned(d->index, 4) || misaligned(d->counts, 4)) return fail(ctx, D2PC_ERR_INVALID_ARG, "index / counts are not aligned to 4 bytes");
+  const size_t sample = bpp == 3 ? 1 : bpp;
+  if (misaligned(d->texture, sample) || d->tex_pitch % sample != 0 || (d->n_frames > 1 && d->tex_frame_stride % sample != 0))
+    return fail(ctx, D2PC_ERR_INVALID_ARG, "the texture is not aligned to its sample type");
+  const Plane tex{d->texture, d->tex_pitch, d->tex_frame_stride, size_t(d->width) * bpp, d->height};
+  if (!tex.fits(d->n_frames, Bound32::Pitch))
+    return fail(ctx, D2PC_ERR_BAD_SIZE, "texture pitch / frame stride too small for %dx%d (or a pitch beyond 2^32)", d->width, d->height);
+  // the clouds as planes of one row, so that extent() is their hull over n_clouds
+  const Plane pts{d->points, cp * 16, d->points_frame_stride_points * 16, cp * 16, 1};
+  const Plane idx{d->index, cp * 4, d->points_frame_stride_points * 4, cp * 4, 1};
+  const Plane cnt{d->counts, size_t(n_clouds) * 4, 0, size_t(n_clouds) * 4, 1};
+  const Plane out{d->out, cp * 32, d->out_frame_stride_points * 32, cp * 32, 1};
+  const uintptr_t o0 = reinterpret_cast<uintptr_t>(out.p), o1 = o0 + out.extent(n_clouds);
+  auto hits = [&](const Plane &in, int n) {
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in.p);
+    return in.p && i0 < o1 && o0 < i0 + in.extent(n);
+  };
+  if (hits(tex, d->n_frames) || hits(pts, n_clouds) || hits(idx, n_clouds) || hits(cnt, 1))
+    return fail(ctx, D2PC_ERR_INVALID_ARG, "out overlaps an input");
+  DeviceGuard guard(ctx->device);
+  if (!guard.ok) return fail(ctx, D2PC_ERR_NO_DEVICE, "cannot select device %d", ctx->device);
+  a.tex = static_cast<const uint8_t *>(d->texture), a.points = d->points, a.index = d->index, a.counts = d->counts, a.out = d->out;
+  a.tex_pitch = uint32_t(d->tex_pitch), a.tex_frame_stride = tex.kernel_frame_stride(d->n_frames);
+  a.points_stride = n_clouds > 1 ? d->points_frame_stride_points : 0, a.out_stride = n_clouds > 1 ? d->out_frame_stride_points : 0;
+  a.pixel_limit = merged ? frame_pixels * uint64_t(d->n_frames) : frame_pixels;
+  a.cloud_points = uint32_t(cp), a.n_clouds = uint32_t(n_clouds), a.merged = merged ? 1u : 0u;
+  a.width = uint32_t(d->width), a.frame_pixels = uint32_t(frame_pixels), a.border = uint32_t(d->border);
+  a.roi_w = d->index ? 1u : uint32_t(d->width - 2 * d->border);  // (no index: the ROI is not empty, checked above)
+  a.div_w = make_fastdiv(a.width), a.div_frame = make_fastdiv(a.frame_pixels), a.div_roi_w = make_fastdiv(a.roi_w);
+  a.stream = static_cast<hipStream_t>(stream);  // NULL = HIP's default stream
+  D2PC_HIP(ctx, launch_texture(a));
   return D2PC_OK;
 }
 

@@ -18,6 +18,7 @@
 //     d2pc_median_device, d2pc_median_roi_device         Bound32::Pitch, FrameRule::WholeRows (rows * pitch); no overlap test
 //     d2pc_fusion_node_callback_device (incoming frame)  Bound32::Pitch, FrameRule::LastRow
 //     d2pc_rig_process_device (the cameras' frames)      Bound32::Plane, FrameRule::LastRow, behind make_geom's own rules
+//     d2pc_texture_device (the texture; d2pc_capi_rig.hip) Bound32::Pitch, FrameRule::LastRow; 16- / 32-bit samples aligned
 // Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -8,6 +8,9 @@
 // restated here -- is chosen by a wave-uniform branch on (stereoRectify structure, form).  Kernels are templated on the
 // input dtype only.  A point's position in the merged cloud is a 32-bit number (the host refuses n * roi_n >= 2^32);
 // its address is formed in 64 bits: the cloud may exceed 4 GiB.
+//
+// Also here, to share this code object: k_texture, the gather behind d2pc_texture_device (any producer's points + a
+// per-pixel plane -> 32-byte PointXYZI / PointXYZRGB records).
 #include "d2pc_compact_common.hpp"
 #include "d2pc_rig.hpp"
 
@@ -217,6 +220,143 @@ __global__ __launch_bounds__(kBlock) void k_rig_scatter(const uint8_t *__restric
     if (((mask[k] >> lane) & 1ull) != 0 && pos < capacity)
       rig_store<D2PC_SCATTER_STORE_NT != 0>(out, out_index, pos, X[k], Y[k], Z[k], f * frame_pixels + vv[k] * g.width + uu[k]);
   }
+}
+
+// ---- k_texture: a producer's points + a per-pixel plane -> 32-byte PointXYZI / PointXYZRGB records -------------------
+// A gather and nothing else (no reprojection arithmetic): per point 16 B read, 4 B of index (none in the PARITY
+// layout), 1-4 B of texture, 32 B written.  Positions are 32-bit, every address is formed in 64 bits.
+// Store mapping: one lane per 16-byte HALF record -- the even lane of a pair copies the point, the odd lane reads index
+// and texture and stores {word, 0, 0, 0} -- so every store instruction of a wave writes 1 KiB contiguously.  The
+// alternative, one lane per record with two 16-byte stores 32 bytes apart, is built by -DD2PC_TEXTURE_LANE_PER_RECORD=1
+// (`make variant`) for tools/ab_texture.sh only: it is 4-13 % slower at every size but one tie (profiles/texture_ab.txt).
+#ifndef D2PC_TEXTURE_LANE_PER_RECORD
+#define D2PC_TEXTURE_LANE_PER_RECORD 0
+#endif
+constexpr uint64_t kTexMaxBlocks = 1u << 16;
+constexpr int kTexSlots = 4;  // records (half records) in flight per lane
+
+// Where the sample of source pixel `pix` of cloud c lies; a pixel outside the declared planes (ok = false) gets the
+// address of pixel 0 of a declared plane, so that the load stays unconditional and inside the planes: its value is dropped.
+__device__ __forceinline__ const uint8_t *texture_addr(const TexArgs &a, uint32_t c, uint32_t pix, uint32_t bpp, bool &ok) {
+  ok = uint64_t(pix) < a.pixel_limit;
+  pix = ok ? pix : 0u;
+  uint32_t f = c;
+  if (a.merged) {  // (launch-uniform)
+    f = fdiv(pix, a.div_frame);
+    pix -= f * a.frame_pixels;
+  }
+  const uint32_t v = fdiv(pix, a.div_w), u = pix - v * a.width;
+  return a.tex + uint64_t(f) * a.tex_frame_stride + uint64_t(v) * uint64_t(a.tex_pitch) + uint64_t(u * bpp);
+}
+
+// The texture words of a lane's kTexSlots records: ONE launch-uniform switch around the loads of all slots, so that they
+// are in flight together.  The source pixel of record i is the producer's index, or the PARITY layout's ROI pixel.
+__device__ __forceinline__ void texture_words(const TexArgs &a, const uint32_t *index, uint32_t c,
+                                              const uint32_t (&rec)[kTexSlots], uint32_t (&w)[kTexSlots]) {
+  uint32_t pix[kTexSlots];
+  if (index) {
+#pragma unroll
+    for (int k = 0; k < kTexSlots; ++k) pix[k] = index[uint64_t(rec[k])];
+  } else {
+#pragma unroll
+    for (int k = 0; k < kTexSlots; ++k) {
+      const uint32_t rv = fdiv(rec[k], a.div_roi_w);
+      pix[k] = (rv + a.border) * a.width + (rec[k] - rv * a.roi_w) + a.border;
+    }
+  }
+  const uint32_t kind = a.kind;
+  const uint32_t bpp = kind == TEX_U16 ? 2u : kind == TEX_F32 ? 4u : (kind == TEX_RGB8 || kind == TEX_BGR8) ? 3u : 1u;
+  const uint8_t *q[kTexSlots];
+  bool ok[kTexSlots];
+#pragma unroll
+  for (int k = 0; k < kTexSlots; ++k) q[k] = texture_addr(a, c, pix[k], bpp, ok[k]);
+  switch (kind) {
+    case TEX_U8:
+#pragma unroll
+      for (int k = 0; k < kTexSlots; ++k) w[k] = __float_as_uint(float(q[k][0]));
+      break;
+    case TEX_U16:
+#pragma unroll
+      for (int k = 0; k < kTexSlots; ++k) w[k] = __float_as_uint(float(*reinterpret_cast<const uint16_t *>(q[k])));
+      break;
+    case TEX_F32:
+#pragma unroll
+      for (int k = 0; k < kTexSlots; ++k) w[k] = *reinterpret_cast<const uint32_t *>(q[k]);
+      break;
+    case TEX_MONO8:
+#pragma unroll
+      for (int k = 0; k < kTexSlots; ++k) w[k] = 0xff000000u | uint32_t(q[k][0]) * 0x010101u;
+      break;
+    default: {
+      uint32_t p0[kTexSlots], p1[kTexSlots], p2[kTexSlots];
+#pragma unroll
+      for (int k = 0; k < kTexSlots; ++k) p0[k] = q[k][0], p1[k] = q[k][1], p2[k] = q[k][2];
+#pragma unroll
+      for (int k = 0; k < kTexSlots; ++k)
+        w[k] = 0xff000000u | p1[k] << 8 | (kind == TEX_RGB8 ? p0[k] << 16 | p2[k] : p2[k] << 16 | p0[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kTexSlots; ++k) w[k] = ok[k] ? w[k] : 0u;
+}
+
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+
+// Loads are unconditional -- a position past the count is clamped to the cloud's last record (the loop runs only for
+// n >= 1), whose bytes are read and dropped -- so that the loads of all slots are issued before the first wait; only
+// the stores are predicated.
+template <bool HALF>
+__global__ __launch_bounds__(kBlock) void k_texture(const TexArgs a) {
+  static_assert(kTexSlots == 4, "the point slots are named");
+  const uint32_t c = blockIdx.y;
+  uint32_t n = a.cloud_points;
+  if (a.counts) {
+    const uint32_t k = a.counts[c];
+    n = k == kCountTimedOut ? 0u : (k < n ? k : n);
+  }
+  const v4u *pts = static_cast<const v4u *>(a.points) + uint64_t(c) * a.points_stride;
+  const uint32_t *index = a.index ? a.index + uint64_t(c) * a.points_stride : nullptr;
+  v4u *out = static_cast<v4u *>(a.out) + 2u * uint64_t(c) * a.out_stride;  // in 16-byte halves
+  constexpr uint32_t kStep = HALF ? uint32_t(kBlock) / 2u : uint32_t(kBlock), kTile = kStep * uint32_t(kTexSlots);
+  const uint32_t lane_rec = HALF ? threadIdx.x >> 1 : threadIdx.x, odd = threadIdx.x & 1u;
+  const uint32_t last = n - 1u;
+  for (uint64_t r0 = uint64_t(blockIdx.x) * kTile; r0 < n; r0 += uint64_t(gridDim.x) * kTile) {
+    const uint64_t i0 = r0 + lane_rec, i1 = i0 + kStep, i2 = i1 + kStep, i3 = i2 + kStep;
+    const uint32_t rec[kTexSlots] = {i0 < n ? uint32_t(i0) : last, i1 < n ? uint32_t(i1) : last,
+                                     i2 < n ? uint32_t(i2) : last, i3 < n ? uint32_t(i3) : last};
+    uint32_t w[kTexSlots];
+    if constexpr (!HALF) {
+      const v4u p0 = pts[uint64_t(rec[0])], p1 = pts[uint64_t(rec[1])], p2 = pts[uint64_t(rec[2])], p3 = pts[uint64_t(rec[3])];
+      texture_words(a, index, c, rec, w);
+      if (i0 < n) out[2u * i0] = p0, out[2u * i0 + 1u] = v4u{w[0], 0u, 0u, 0u};
+      if (i1 < n) out[2u * i1] = p1, out[2u * i1 + 1u] = v4u{w[1], 0u, 0u, 0u};
+      if (i2 < n) out[2u * i2] = p2, out[2u * i2 + 1u] = v4u{w[2], 0u, 0u, 0u};
+      if (i3 < n) out[2u * i3] = p3, out[2u * i3 + 1u] = v4u{w[3], 0u, 0u, 0u};
+    } else {
+      v4u h0, h1, h2, h3;
+      if (odd) {  // one divergence for the four slots: the odd lanes' index and sample loads, the even lanes' point loads
+        texture_words(a, index, c, rec, w);
+        h0 = v4u{w[0], 0u, 0u, 0u}, h1 = v4u{w[1], 0u, 0u, 0u}, h2 = v4u{w[2], 0u, 0u, 0u}, h3 = v4u{w[3], 0u, 0u, 0u};
+      } else {
+        h0 = pts[uint64_t(rec[0])], h1 = pts[uint64_t(rec[1])], h2 = pts[uint64_t(rec[2])], h3 = pts[uint64_t(rec[3])];
+      }
+      if (i0 < n) out[2u * i0 + odd] = h0;
+      if (i1 < n) out[2u * i1 + odd] = h1;
+      if (i2 < n) out[2u * i2 + odd] = h2;
+      if (i3 < n) out[2u * i3 + odd] = h3;
+    }
+  }
+}
+
+hipError_t launch_texture(const TexArgs &a) {
+  constexpr bool half = D2PC_TEXTURE_LANE_PER_RECORD == 0;
+  const uint64_t tile = uint64_t(kBlock) / (half ? 2u : 1u) * kTexSlots;
+  // one-shot blocks up to 2^16 per cloud (33 million records), a stride loop beyond; a block past the cloud's count
+  // leaves at once
+  const uint64_t tiles = (uint64_t(a.cloud_points) + tile - 1) / tile;
+  const dim3 grid(uint32_t(tiles < kTexMaxBlocks ? tiles : kTexMaxBlocks), a.n_clouds);
+  hipLaunchKernelGGL(k_texture<half>, grid, dim3(kBlock), 0, a.stream, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_rig_parity(const RigArgs &a) {

@@ -42,4 +42,30 @@ struct RigArgs {
 hipError_t launch_rig_parity(const RigArgs &a);
 hipError_t launch_rig_compact(const RigArgs &a);  // count, scan, scatter
 
+// d2pc_texture_device: the gather that turns a producer's 16-byte points into 32-byte PointXYZI / PointXYZRGB records
+// (k_texture lives beside the rig's kernels to share their code object: a translation unit of its own costs ~10 KB of
+// the product library's size budget).
+enum : uint32_t { TEX_U8 = 0, TEX_U16 = 1, TEX_F32 = 2, TEX_RGB8 = 3, TEX_BGR8 = 4, TEX_MONO8 = 5 };
+struct TexArgs {
+  const uint8_t *tex = nullptr;     // device: n_frames planes
+  const void *points = nullptr;     // device: 16-byte records
+  const uint32_t *index = nullptr;  // device, nullable (PARITY layout)
+  const uint32_t *counts = nullptr; // device, nullable
+  void *out = nullptr;              // device: 32-byte records
+  uint64_t tex_frame_stride = 0;    // bytes
+  uint64_t points_stride = 0;       // points between clouds (points and index)
+  uint64_t out_stride = 0;          // records between clouds
+  uint64_t pixel_limit = 0;         // an index at or beyond it reads nothing: W * H, merged: n_frames * W * H (<= 2^32)
+  uint32_t tex_pitch = 0;           // bytes (< 2^32; row * pitch is formed in 64 bits)
+  uint32_t cloud_points = 0;
+  uint32_t n_clouds = 0;            // grid.y
+  uint32_t width = 0, frame_pixels = 0;
+  uint32_t border = 0, roi_w = 0;   // PARITY layout only
+  uint32_t kind = TEX_U8;
+  uint32_t merged = 0;
+  FastDiv div_w{}, div_frame{}, div_roi_w{};
+  hipStream_t stream = nullptr;
+};
+hipError_t launch_texture(const TexArgs &a);
+
 }  // namespace d2pc

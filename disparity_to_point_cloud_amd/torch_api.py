@@ -87,6 +87,69 @@ class RigBatch:
         return self.points[:n].cpu().numpy(), idx, counts, offsets
 
 
+_T2TEX = {torch.uint8: capi.TEX_U8, torch.uint16: capi.TEX_U16, torch.float32: capi.TEX_F32}
+
+
+def texture_cloud(ctx: capi.Context, points, texture, index=None, counts=None, merged=False, rgb=None, border=None,
+                  n_points=None, is_dense=False, out=None, stream=None):
+    """d2pc_texture_device on torch CUDA tensors: the 32-byte PointXYZI / PointXYZRGB records of a cloud this library
+    made (DeviceBatch / RigBatch or any d2pc_process*_device result) and a per-pixel plane of the source frames.
+
+    points: (F, stride, 4) float32, one cloud per frame (DeviceBatch.points), or (capacity, 4): one frame's cloud, or
+    with merged=True a rig's merged cloud (RigBatch.points).  index / counts: the producer's tensors; for a rig pass
+    counts = offsets[n:].  index=None is the PARITY layout (`border` defaults to the context's).
+    texture: (F, H, W) or (H, W) of uint8 / uint16 / float32 -> XYZI; with rgb="mono8" a uint8 plane -> XYZRGB;
+    (F, H, W, 3) or (H, W, 3) uint8 with rgb="rgb8" / "bgr8" -> XYZRGB.  Unit sample stride; row and frame strides
+    are free, so cropped views work.
+    Returns (records, meta): records as float32 of shape points.shape[:-1] + (8,) (`.view(torch.uint8)` gives the
+    PointCloud2 bytes), written for each cloud's count only; meta = d2pc_textured_cloud_meta for n_points (default:
+    the capacity of one cloud, which in PARITY is the cloud) and is_dense -- properties of the CLOUD, which may have
+    been made earlier and in another mode than the context is in now: a COMPACT cloud passes is_dense=True and, once
+    it has read the count, n_points.  Asynchronous on `stream` (default: torch's current
+    stream); no torch op computes anything here."""
+    assert points.is_cuda and points.dtype == torch.float32 and points.shape[-1] == 4 and points.is_contiguous()
+    assert points.dim() in (2, 3) and not (merged and points.dim() == 3)
+    packed = rgb in ("rgb8", "bgr8")
+    assert rgb in (None, "mono8", "rgb8", "bgr8") and texture.is_cuda
+    planes = texture.dim() - (1 if packed else 0)
+    assert planes in (2, 3) and (not packed or (texture.shape[-1] == 3 and texture.stride(-1) == 1))
+    col = -2 if packed else -1
+    assert texture.stride(col) == (3 if packed else 1)
+    f = texture.shape[0] if planes == 3 else 1
+    h, w = texture.shape[col - 1], texture.shape[col]
+    if rgb is not None:
+        assert texture.dtype == torch.uint8
+        fmt = {"mono8": capi.TEX_MONO8, "rgb8": capi.TEX_RGB8, "bgr8": capi.TEX_BGR8}[rgb]
+    else:
+        fmt = _T2TEX[texture.dtype]
+    es = texture.element_size()
+    n_clouds = 1 if merged else f
+    assert (points.shape[0] if points.dim() == 3 else 1) == n_clouds
+    cap = points.shape[-2]
+    if out is None:
+        out = torch.empty(tuple(points.shape[:-1]) + (8,), dtype=torch.float32, device=points.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(points.shape[:-1]) + (8,)
+    cloud_points = cap
+    if index is None:
+        border = ctx.config().border if border is None else border
+        cloud_points = capi.roi_points(w, h, border)
+    else:
+        assert index.is_cuda and index.element_size() == 4 and index.is_contiguous() and tuple(index.shape) == tuple(points.shape[:-1])
+    if counts is not None:
+        assert counts.is_cuda and counts.element_size() == 4 and counts.is_contiguous() and counts.numel() >= n_clouds
+    desc = capi.texture_desc_init(
+        point_format=capi.POINT_XYZI if rgb is None else capi.POINT_XYZRGB, texture_format=fmt, width=w, height=h,
+        border=border or 0, n_frames=f, merged=int(bool(merged)), texture=texture.data_ptr(),
+        tex_pitch=texture.stride(col - 1) * es, tex_frame_stride=texture.stride(0) * es if planes == 3 else 0,
+        points=points.data_ptr(), index=index.data_ptr() if index is not None else None,
+        counts=counts.data_ptr() if counts is not None else None, cloud_points=cloud_points,
+        points_frame_stride_points=cap, out=out.data_ptr(), out_frame_stride_points=cap)
+    s = stream if stream is not None else torch.cuda.current_stream(points.device)
+    ctx.texture_device(desc, s.cuda_stream)
+    meta = capi.textured_cloud_meta(desc.point_format, cloud_points if n_points is None else n_points, is_dense)
+    return out, meta
+
+
 def fuse_planes(ctx: capi.Context, planes, rule=capi.FUSE_GRAD_FILTER, crop=(0, 40, 30, 10), want_combined=True,
                 stream=None):
     """d2pc_fuse_device on torch uint8 CUDA tensors.

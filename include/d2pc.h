@@ -722,6 +722,97 @@ int d2pc_rig_process_device(d2pc_rig *rig, const void *d_frames, float scale, si
                             size_t capacity_points, uint32_t *d_counts, uint32_t *d_offsets, void *stream);
 int d2pc_rig_destroy(d2pc_rig *rig);
 
+/*
+ * TEXTURED clouds: pcl::PointXYZI / pcl::PointXYZRGB records (32 bytes) made from a cloud this library produced and a
+ * per-pixel plane aligned with the disparity grid (the camera image; the fusion node's COMBINED_SCORE).  The texture
+ * is attached BEHIND the producer by one memory-bound gather: every producer above already leaves each point's source
+ * pixel (d_out_index) and the counts on the device, so one entry point serves every mode, every reproject form, the
+ * callback body and the rig, and the first 16 bytes of a record are the producer's bytes by construction.
+ *
+ *   D2PC_POINT_XYZI    {x, y, z, 1.0f | intensity, 0, 0, 0}: intensity = (float)sample for the 8- and 16-bit texture
+ *                      formats (exact), a bit copy of the sample for D2PC_TEX_F32 (NaN payloads included).  PCL leaves
+ *                      the record's last 12 bytes indeterminate; here they are zero.
+ *   D2PC_POINT_XYZRGB  {x, y, z, 1.0f | rgb, 0, 0, 0}: rgb is the 32-bit word (255 << 24) | (r << 16) | (g << 8) | b,
+ *                      in memory the bytes b, g, r, 255.  Alpha 255 is what the constructors of PCL >= 1.8 set
+ *                      (stereo_image_proc leaves 0): a documented choice, no release is pinned.  D2PC_TEX_RGB8 and
+ *                      D2PC_TEX_BGR8 are packed 3-byte pixels (any pitch >= 3 W, no alignment); D2PC_TEX_MONO8 gives
+ *                      r = g = b.
+ * The point's 16 bytes are copied bit for bit (the pad 1.0f, a NaN coordinate).
+ */
+typedef enum d2pc_point_format { D2PC_POINT_XYZI = 1, D2PC_POINT_XYZRGB = 2 } d2pc_point_format;
+typedef enum d2pc_texture_format {
+  D2PC_TEX_U8 = 1,      /* XYZI   */
+  D2PC_TEX_U16 = 2,     /* XYZI   */
+  D2PC_TEX_F32 = 3,     /* XYZI   */
+  D2PC_TEX_RGB8 = 4,    /* XYZRGB */
+  D2PC_TEX_BGR8 = 5,    /* XYZRGB */
+  D2PC_TEX_MONO8 = 6    /* XYZRGB */
+} d2pc_texture_format;
+
+typedef struct d2pc_texture_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_texture_desc) */
+  int32_t point_format;        /* d2pc_point_format */
+  int32_t texture_format;      /* d2pc_texture_format; must belong to the point format */
+  int32_t width, height;       /* of the source frames the cloud was made from (and of the texture) */
+  int32_t border;              /* the producer's border; read only when `index` is NULL */
+  int32_t n_frames;            /* source frames = texture planes, 1 .. 65,535 */
+  int32_t merged;              /* 0: n_frames clouds, cloud f from frame f, index v * width + u (what d2pc_process_device and
+                                  d2pc_process_mono_device write); 1: ONE cloud, index f * width * height + v * width + u
+                                  (what d2pc_rig_process_device writes) */
+  const void *texture;         /* DEVICE: n_frames planes of height rows */
+  size_t tex_pitch;            /* bytes between rows */
+  size_t tex_frame_stride;     /* bytes between planes (ignored when n_frames == 1) */
+  const void *points;          /* DEVICE: the producer's 16-byte records, 16-byte aligned */
+  const uint32_t *index;       /* DEVICE, nullable: the producer's d_out_index.  NULL = the PARITY layout, merged 0 only:
+                                  position i is ROI pixel (border + i / (width - 2 border), border + i % (width - 2 border))
+                                  and cloud_points must equal d2pc_roi_points(width, height, border) */
+  const uint32_t *counts;      /* DEVICE, nullable: points of each cloud (the producer's d_counts; for a rig pass
+                                  d_offsets + n_cameras, the merged cloud's total).  NULL = cloud_points each.  A count
+                                  above cloud_points is clamped; 0xFFFFFFFF (the in-band failure mark of
+                                  d2pc_process_device) counts as 0 */
+  size_t cloud_points;         /* records one cloud may hold, 1 .. 2^32 - 1 */
+  size_t points_frame_stride_points;  /* points between the clouds in `points` and in `index` (ignored for one cloud) */
+  void *out;                   /* DEVICE out: 32-byte records, 16-byte aligned */
+  size_t out_frame_stride_points;     /* records between the clouds in `out` (ignored for one cloud) */
+} d2pc_texture_desc;
+
+/* struct_size, D2PC_POINT_XYZI, D2PC_TEX_U8, n_frames 1; everything else zero. */
+void d2pc_texture_desc_init(d2pc_texture_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream); allocates nothing, so it can be captured into a graph as
+ * it is, behind its producer.  The context supplies the device and d2pc_last_error only: border and layout come from
+ * the descriptor, so a cloud made earlier can be textured later.  Record i of a cloud is written for
+ * i < min(cloud_points, count); records beyond stay untouched.  An index at or beyond the declared pixels (width x
+ * height, merged: n_frames x width x height) gives texture word 0 and reads nothing.  No host round trip: the counts
+ * are read on the device.
+ * Refused before anything is enqueued: NULL or a wrong struct_size (D2PC_ERR_INVALID_ARG); an unknown format or a
+ * texture format of the other point format (D2PC_ERR_BAD_DTYPE); width, height, n_frames <= 0, border < 0, width x
+ * height > 2^31, merged n_frames x width x height > 2^32, cloud_points 0 or >= 2^32, a NULL index whose cloud_points is
+ * not d2pc_roi_points, a texture plane that does not fit its pitch (< 2^32) or frame stride, a frame stride below
+ * cloud_points or beyond 2^40 points, a tex_frame_stride beyond 2^46 bytes (D2PC_ERR_BAD_SIZE); a NULL index with merged 1, points / out not 16-byte aligned, a 16- or 32-bit
+ * texture (base, pitch, frame stride), index or counts not aligned to their sample, `out` overlapping any input
+ * (D2PC_ERR_INVALID_ARG).
+ */
+int d2pc_texture_device(d2pc_ctx *ctx, const d2pc_texture_desc *desc, void *stream);
+
+/* sensor_msgs/PointCloud2 metadata of n textured records, as pcl::toROSMsg fills it for pcl::PointXYZI /
+ * pcl::PointXYZRGB: point_step 32, row_step 32 n, fields x, y, z at 0 / 4 / 8 and "intensity" or "rgb" at 16, all
+ * FLOAT32 (7), count 1.  ("intensity" does not fit d2pc_field's 8 bytes: a field type of its own.)  Host only, no
+ * context.  D2PC_ERR_INVALID_ARG for NULL, D2PC_ERR_BAD_DTYPE for an unknown format, D2PC_ERR_BAD_SIZE when 32 n does
+ * not fit 32 bits. */
+typedef struct d2pc_textured_field { char name[12]; uint32_t offset; uint8_t datatype; uint32_t count; } d2pc_textured_field;
+typedef struct d2pc_textured_cloud_meta {
+  uint32_t height;        /* 1                                                */
+  uint32_t width;         /* n                                                */
+  uint32_t point_step;    /* 32 = sizeof(pcl::PointXYZI / pcl::PointXYZRGB)   */
+  uint32_t row_step;      /* 32*n                                             */
+  uint8_t is_bigendian;   /* 0                                                */
+  uint8_t is_dense;       /* as given                                         */
+  uint32_t n_fields;      /* 4                                                */
+  d2pc_textured_field fields[4];
+} d2pc_textured_cloud_meta;
+int d2pc_textured_cloud_meta_fill(int point_format, size_t n_points, int is_dense, d2pc_textured_cloud_meta *meta);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,9 @@ def main():
                                                   "only frames/split write fronts are live at a time")
     ap.add_argument("--ring", type=int, default=1, help="camera-shaped launches: RING x frames distinct input frames (and output slots), every launch "
                                                         "takes the next `frames` of them, so no launch finds its input in the Infinity Cache")
+    ap.add_argument("--texture", default="", choices=["", "u8", "u16", "f32", "rgb8", "bgr8", "mono8"],
+                    help="time d2pc_texture_device ALONE on the cloud each candidate's warm-up launch produced (the attach of a texture of "
+                         "this format; --idx 0 in parity mode: the PARITY layout without an index)")
     ap.add_argument("--w", type=int, default=3840)
     ap.add_argument("--h", type=int, default=2160)
     a = ap.parse_args()
@@ -79,6 +82,10 @@ def main():
     index = torch.empty((NF * max_stride + max(ioffs) + 64,), dtype=torch.int32, device="cuda") if a.idx else None
     counts = torch.zeros((NF,), dtype=torch.int32, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
+    if a.texture:
+        tbpp = {"u8": 1, "u16": 2, "f32": 4, "rgb8": 3, "bgr8": 3, "mono8": 1}[a.texture]
+        tex = torch.randint(0, 256, (NF, a.h, a.w * tbpp), generator=g, device="cuda", dtype=torch.int32).to(torch.uint8)
+        records = torch.empty((NF * max_stride + max(ooffs) + 16, 8), dtype=torch.float32, device="cuda")
 
     class Cand:
         def __init__(self, ctx, oalign, ooff, ioff=0, oextra=0, split=1):
@@ -89,7 +96,20 @@ def main():
             self.out_ptr = pool.data_ptr() + 16 * ooff
             self.idx_ptr = index.data_ptr() + 4 * ioff if index is not None else None
             ctx.reserve(W, H, F)
+        def texture_desc(self, border, with_index):
+            """the attach over the first F clouds, as this candidate's producer laid them out"""
+            self.desc = capi.texture_desc_init(
+                point_format=capi.POINT_XYZI if tbpp != 3 and a.texture != "mono8" else capi.POINT_XYZRGB,
+                texture_format={"u8": capi.TEX_U8, "u16": capi.TEX_U16, "f32": capi.TEX_F32, "rgb8": capi.TEX_RGB8,
+                                "bgr8": capi.TEX_BGR8, "mono8": capi.TEX_MONO8}[a.texture],
+                width=W, height=H, border=border, n_frames=F, texture=tex.data_ptr(), tex_pitch=W * tbpp, tex_frame_stride=W * H * tbpp,
+                points=self.out_ptr, index=self.idx_ptr if with_index else None, counts=counts.data_ptr(),
+                cloud_points=capi.roi_points(W, H, border), points_frame_stride_points=self.stride,
+                out=records.data_ptr(), out_frame_stride_points=self.stride)
         def launch(self):
+            if getattr(self, "desc", None) is not None:
+                self.ctx.texture_device(self.desc, stream)
+                return
             n = F // self.split
             base = self.pos * F
             self.pos = (self.pos + 1) % a.ring
@@ -125,6 +145,10 @@ def main():
             npts = int(counts.sum().item()) // a.ring
             roi_n = capi.roi_points(W, H, int(border))
             alg = esize * F * roi_n + (20 if a.idx else 16) * npts
+            if a.texture:   # from here on the candidate's launch is the attach alone: 16 B + index + sample read, 32 B written per point
+                b.texture_desc(int(border), bool(a.idx))
+                alg = (16 + (4 if a.idx else 0) + tbpp + 32) * npts
+                b.launch(); torch.cuda.synchronize()
             cands.append((f"{lib:8s} {mode:7s} b={border:>2s} pxt={pxt:>2s} bpc={bpc:>2s} novec={nv} algo={algo} oalign={oal} ooff={oof} form={form} {tune}" + (f" ioff={iof}" if len(ioffs) > 1 else "") + (f" oextra={oex}" if len(oextras) > 1 else "") + (f" split={spl}" if len(splits) > 1 else ""), b, alg, []))
     for r in range(a.rounds):
         for label, b, alg, ts in cands:

@@ -86,6 +86,19 @@ from .capi import (  # noqa: F401
     texture_desc_init,
     textured_cloud_meta,
 )
+from .sectors import (  # noqa: F401  (include/d2pc_sectors.h: the companion library libd2pc_sectors.so)
+    Sectors,
+    SectorsConfig,
+    SectorsDesc,
+    SectorsGeometry,
+    load_sectors_library,
+    sectors_config_init,
+    sectors_desc_check,
+    sectors_desc_init,
+    sectors_geometry,
+    sectors_library_path,
+    sectors_table,
+)
 
 
 def __getattr__(name):

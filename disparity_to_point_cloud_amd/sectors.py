@@ -1,0 +1,201 @@
+"""ctypes binding of include/d2pc_sectors.h: the obstacle sectors of the companion library libd2pc_sectors.so.
+
+One-to-one with the header: every function it declares is bound here and nothing else.  No compute: a polar
+min-range grid is made on the device, behind the producer of the cloud, or not at all.
+"""
+import ctypes
+import os
+
+import numpy as np
+
+from .capi import D2pcError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+
+MAX_SECTORS, MAX_LAYERS, SHARE_POINTS = 360, 16, 1024
+EMPTY = 0xFFFFFFFF   # `nearest` of an empty cell
+
+# every symbol include/d2pc_sectors.h declares (tests check the library exports all of them and nothing else)
+SECTORS_SYMBOLS = [
+    "d2pc_sectors_config_init", "d2pc_sectors_geometry", "d2pc_sectors_table", "d2pc_sectors_create",
+    "d2pc_sectors_destroy", "d2pc_sectors_last_error", "d2pc_sectors_blocks", "d2pc_sectors_desc_init",
+    "d2pc_sectors_desc_check", "d2pc_sectors_process_device",
+]
+
+
+class SectorsConfig(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("device_id", ctypes.c_int32), ("n_sectors", ctypes.c_int32),
+        ("n_layers", ctypes.c_int32), ("azimuth0", ctypes.c_double), ("r_min", ctypes.c_float), ("r_max", ctypes.c_float),
+        ("u_min", ctypes.c_float), ("u_max", ctypes.c_float), ("axes", ctypes.c_int32 * 3), ("min_count", ctypes.c_int32),
+        ("no_obstacle_cm", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+class SectorsGeometry(ctypes.Structure):
+    _fields_ = [
+        ("n_cells", ctypes.c_int32), ("table_entries", ctypes.c_int32), ("rmin2", ctypes.c_float), ("rmax2", ctypes.c_float),
+        ("inv_h", ctypes.c_float), ("share_points", ctypes.c_int32), ("blocks_per_cu", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32), ("lds_bytes", ctypes.c_size_t), ("block_bytes", ctypes.c_size_t),
+        ("device_bytes", ctypes.c_size_t), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+class SectorsDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("point_step", ctypes.c_int32), ("n_clouds", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("points", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+        ("cloud_points", ctypes.c_size_t), ("points_frame_stride_points", ctypes.c_size_t), ("range", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("nearest", ctypes.c_void_p), ("distance_cm", ctypes.c_void_p),
+    ]
+
+
+_lib = None
+
+
+def sectors_library_path(variant=None) -> str:
+    return os.path.join(_HERE, "libd2pc_sectors.so" if variant is None else "libd2pc_sectors_%s.so" % variant)
+
+
+def load_sectors_library(variant=None):
+    """Load libd2pc_sectors.so (`variant`: libd2pc_sectors_<variant>.so, the A/B builds of tools/sectors_bench.py; not
+    cached).  Raises, never falls back, when it is not built."""
+    global _lib
+    if variant is None and _lib is not None:
+        return _lib
+    path = sectors_library_path(variant)
+    if not os.path.exists(path):
+        raise ImportError(
+            f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
+    # torch ships its own HIP runtime; import it first so both share ONE (as capi.load_library does)
+    try:
+        import torch  # noqa: F401
+    except Exception:  # torch is plumbing only; the ABI works without it
+        pass
+    L = ctypes.CDLL(path)
+    vp, fp = ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)
+    cfg, desc = ctypes.POINTER(SectorsConfig), ctypes.POINTER(SectorsDesc)
+    L.d2pc_sectors_config_init.argtypes = [cfg]
+    L.d2pc_sectors_config_init.restype = None
+    L.d2pc_sectors_geometry.argtypes = [cfg, ctypes.POINTER(SectorsGeometry)]
+    L.d2pc_sectors_table.argtypes = [cfg, fp, fp, ctypes.c_int]
+    L.d2pc_sectors_create.argtypes = [cfg, ctypes.POINTER(vp)]
+    L.d2pc_sectors_destroy.argtypes = [vp]
+    L.d2pc_sectors_last_error.argtypes = [vp]
+    L.d2pc_sectors_last_error.restype = ctypes.c_char_p
+    L.d2pc_sectors_blocks.argtypes = [vp]
+    L.d2pc_sectors_desc_init.argtypes = [desc]
+    L.d2pc_sectors_desc_init.restype = None
+    L.d2pc_sectors_desc_check.argtypes = [cfg, desc]
+    L.d2pc_sectors_process_device.argtypes = [vp, desc, vp]
+    if variant is None:
+        _lib = L
+    return L
+
+
+def _set(struct, kw):
+    fields = dict(struct._fields_)
+    for k, v in kw.items():
+        if k not in fields:
+            raise TypeError("%s has no field %r" % (type(struct).__name__, k))
+        setattr(struct, k, tuple(v) if k == "axes" else v)
+    return struct
+
+
+def sectors_config_init(**kw) -> SectorsConfig:
+    """d2pc_sectors_config_init, then the given fields."""
+    c = SectorsConfig()
+    load_sectors_library().d2pc_sectors_config_init(ctypes.byref(c))
+    return _set(c, kw)
+
+
+def sectors_desc_init(**kw) -> SectorsDesc:
+    """d2pc_sectors_desc_init, then the given fields."""
+    d = SectorsDesc()
+    load_sectors_library().d2pc_sectors_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_geometry(cfg: SectorsConfig) -> SectorsGeometry:
+    """d2pc_sectors_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = SectorsGeometry()
+    st = load_sectors_library().d2pc_sectors_geometry(ctypes.byref(cfg), ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "sectors_geometry(%d x %d)" % (cfg.n_sectors, cfg.n_layers))
+    return g
+
+
+def sectors_table(cfg: SectorsConfig):
+    """d2pc_sectors_table: the boundary directions (c, s), two float32 arrays of n_sectors / 2."""
+    c = np.zeros(MAX_SECTORS // 2, dtype=np.float32)
+    s = np.zeros(MAX_SECTORS // 2, dtype=np.float32)
+    fp = ctypes.POINTER(ctypes.c_float)
+    n = load_sectors_library().d2pc_sectors_table(ctypes.byref(cfg), c.ctypes.data_as(fp), s.ctypes.data_as(fp), len(c))
+    if n <= 0:
+        raise D2pcError(-n, "sectors_table(%d)" % cfg.n_sectors)
+    return c[:n].copy(), s[:n].copy()
+
+
+def sectors_desc_check(cfg: SectorsConfig, desc: SectorsDesc) -> int:
+    """d2pc_sectors_desc_check: the status d2pc_sectors_process_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_desc_check(ctypes.byref(cfg), ctypes.byref(desc))
+
+
+def _ptr(x):
+    """A raw device pointer of a torch tensor, an int, or None."""
+    return x.data_ptr() if hasattr(x, "data_ptr") else x
+
+
+class Sectors:
+    """d2pc_sectors_*: one session = one grid geometry on one device.  `process` takes torch tensors or raw device
+    pointers, is asynchronous on `stream` and allocates nothing."""
+
+    def __init__(self, cfg: SectorsConfig = None, variant=None, **kw):
+        self._L, self._h = load_sectors_library(variant), None
+        self.cfg = _set(cfg, kw) if cfg is not None else sectors_config_init(**kw)
+        h = ctypes.c_void_p()
+        st = self._L.d2pc_sectors_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if st:
+            raise D2pcError(st, "sectors_create(%d x %d)" % (self.cfg.n_sectors, self.cfg.n_layers))
+        self._h = h
+        self.geometry = sectors_geometry(self.cfg)
+        self.n_cells, self.blocks = self.geometry.n_cells, int(self._L.d2pc_sectors_blocks(h))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.d2pc_sectors_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def last_error(self) -> str:
+        return self._L.d2pc_sectors_last_error(self._h).decode()
+
+    def process_desc(self, desc: SectorsDesc, stream_ptr=None):
+        """d2pc_sectors_process_device."""
+        st = self._L.d2pc_sectors_process_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def process(self, points, cloud_points, point_step=16, n_clouds=1, counts=None, frame_stride_points=0, range=None,
+                count=None, nearest=None, distance_cm=None, stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.process_desc(sectors_desc_init(
+            point_step=point_step, n_clouds=n_clouds, points=_ptr(points), counts=_ptr(counts), cloud_points=cloud_points,
+            points_frame_stride_points=frame_stride_points, range=_ptr(range), count=_ptr(count), nearest=_ptr(nearest),
+            distance_cm=_ptr(distance_cm)), stream_ptr)

@@ -1,0 +1,160 @@
+/*
+ * d2pc_sectors.h -- C ABI of the OBSTACLE SECTORS: a polar min-range grid made on the device from any cloud this
+ * project produces.  The companion library libd2pc_sectors.so exports it; it links the HIP runtime only and needs
+ * nothing of libd2pc.so or of a d2pc_ctx (this header includes d2pc.h for d2pc_status alone).
+ *
+ * A cloud of an omnidirectional rig exists so that an avoidance stack can ask "how far is the nearest obstacle in each
+ * direction": the 72-sector OBSTACLE_DISTANCE record of MAVLink, the polar histogram a local planner builds first.
+ * This call answers it behind the producer, on the producer's stream, and leaves n_sectors x n_layers cells in device
+ * memory -- 144 bytes for the default grid instead of the 50-70 MB of the cloud.
+ *
+ * Plain C: pointers and sizes only.  Every function returns a d2pc_status and never throws or aborts.  No CPU path:
+ * without a usable gfx950 device d2pc_sectors_create fails with D2PC_ERR_NO_DEVICE.  A session is not thread-safe.
+ *
+ * ---------------------------------------------------------------------------------------------------- SPECIFICATION
+ * Exact, so that float32 arithmetic with ONE rounding per operation (no fused multiply-add) reproduces every bit;
+ * fl() below is that rounding.  tests/sectors_ref.py restates it in numpy.
+ *
+ * Per point.  The record's first three floats are x, y, z.  axes[3] picks forward, left and up from them: each pick is
+ * +-1, +-2 or +-3 (x, y, z; a negative pick negates, which is exact) and the magnitudes are distinct:
+ *     f = pick(axes[0]),  l = pick(axes[1]),  u = pick(axes[2])
+ * The optical frame of a camera (x right, y down, z forward) is {+3, -1, -2}; a body frame x forward, y left, z up is
+ * {+1, +2, +3}.  Negating the pick of `l` makes the sectors run clockwise seen from above (MAVLink's numbering).
+ *
+ * Gate.  A point takes part if and only if
+ *     x, y and z are finite
+ *     r2 = fl(fl(f*f) + fl(l*l)) > 0
+ *     rmin2 <= r2 <= rmax2,  rmin2 = fl(r_min*r_min), rmax2 = fl(r_max*r_max) formed once on the host (r_max = +inf
+ *                            is allowed; so is r2 = +inf then)
+ *     u_min <= u < u_max     (-inf / +inf: no gate; both finite and u_min < u_max when n_layers > 1)
+ *
+ * Layer.  0 when n_layers = 1, otherwise min(n_layers - 1, (int)floorf(fl(fl(u - u_min) * inv_h))) with
+ *     inv_h = (float)(n_layers / ((double)u_max - (double)u_min)), formed on the host (d2pc_sectors_geometry returns it)
+ *
+ * Sector.  n = n_sectors is even.  azimuth0 (radians, double) is the direction of the boundary between the last sector
+ * and sector 0, measured from f towards l.  The boundary table holds n/2 directions, evaluated in double and rounded
+ * once:  c_j = (float)cos(azimuth0 + 2 pi j / n),  s_j = (float)sin(azimuth0 + 2 pi j / n),  j = 0 .. n/2 - 1
+ * (d2pc_sectors_table returns it).  With
+ *     cross_j(f, l) = fl(fl(c_j*l) - fl(s_j*f))          dot_0 = fl(fl(c_0*f) + fl(s_0*l))
+ *     h  = cross_0 < 0  or  (cross_0 == 0 and dot_0 < 0)       the far half: if h, negate f and l
+ *     k' = the number of j in 1 .. n/2 - 1 with cross_j(f, l) >= 0
+ * the sector is k' + h * n/2.  This COUNT is the definition: it is total and needs no atan2, whatever rounding does to
+ * a point next to a boundary; away from a boundary it is the sector float64 atan2 binning gives.
+ *
+ * Cell.  cell = layer * n_sectors + sector.  Its key is the minimum, as an unsigned 64-bit number, over the cell's
+ * points of (bits(r2) << 32) | position, where position = cloud * points_frame_stride_points + record is the point's
+ * place in `points`.  Non-negative floats order as their bit patterns, so the key holds the smallest r2 and, among
+ * equal r2, the smallest position: the result does not depend on the order in which the device visits the points.
+ * The empty key is all ones.  All clouds of a call reduce into ONE grid: they are one instant of one vehicle.
+ *
+ * Outputs, n_cells entries each, all nullable but one:
+ *     range        float32  sqrtf(smallest r2), correctly rounded; +inf when count < min_count
+ *     count        uint32   the cell's points
+ *     nearest      uint32   the key's low word (the position of the closest point); 0xFFFFFFFF for an empty cell;
+ *                           NOT masked by min_count
+ *     distance_cm  uint16   no_obstacle_cm when count < min_count, otherwise fl(range * 100.0f) truncated towards zero
+ *                           and clamped to 65534 (OBSTACLE_DISTANCE's form; MAVLink asks for max_distance + 1 where
+ *                           nothing is seen; marking sectors no camera covers as 65535 is the caller's)
+ */
+#ifndef D2PC_SECTORS_H
+#define D2PC_SECTORS_H
+
+#include "d2pc.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define D2PC_SECTORS_MAX_SECTORS 360
+#define D2PC_SECTORS_MAX_LAYERS 16
+#define D2PC_SECTORS_SHARE_POINTS 1024   /* records one block takes per step of its walk */
+
+typedef struct d2pc_sectors_config {   /* fixed for a session */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_config) */
+  int32_t device_id;
+  int32_t n_sectors;           /* even, 2 .. D2PC_SECTORS_MAX_SECTORS */
+  int32_t n_layers;            /* 1 .. D2PC_SECTORS_MAX_LAYERS height slabs between u_min and u_max */
+  double azimuth0;             /* radians, finite: where sector 0 begins, from f towards l */
+  float r_min, r_max;          /* horizontal range gate, 0 <= r_min <= r_max; r_max may be +inf */
+  float u_min, u_max;          /* height gate u_min <= u < u_max; -inf / +inf for none when n_layers = 1 */
+  int32_t axes[3];             /* f, l, u: +-1, +-2, +-3 of distinct magnitudes */
+  int32_t min_count;           /* >= 1: cells with fewer points report no obstacle in range / distance_cm */
+  uint32_t no_obstacle_cm;     /* <= 65535: distance_cm of such a cell */
+  int32_t reserved[4];         /* zero */
+} d2pc_sectors_config;
+/* 72 x 1, azimuth0 = -pi/72 (sector 0 centred on forward), r 0.2 .. +inf, u -inf .. +inf, axes {3, -1, -2} (a camera's
+ * optical frame, counter-clockwise), min_count 1, no_obstacle_cm 65535, device 0. */
+void d2pc_sectors_config_init(d2pc_sectors_config *cfg);
+
+typedef struct d2pc_sectors_geometry_t {
+  int32_t n_cells;             /* n_sectors * n_layers: entries of every output */
+  int32_t table_entries;       /* n_sectors / 2 */
+  float rmin2, rmax2, inv_h;   /* as the specification forms them; inv_h is 0 when n_layers = 1 */
+  int32_t share_points;        /* D2PC_SECTORS_SHARE_POINTS */
+  int32_t blocks_per_cu;       /* blocks of the reducing kernel per compute unit: as many as the tables in LDS allow, 4
+                                  at the most; a session holds blocks_per_cu x the device's compute units of them */
+  int32_t reserved0;
+  size_t lds_bytes;            /* of one block: the cells' keys and counts and the boundary table */
+  size_t block_bytes;          /* device memory the session holds PER BLOCK (its slab of partial cells); the session
+                                  adds the boundary table, 8 * table_entries bytes */
+  size_t device_bytes;         /* what a session holds on an MI355X (256 compute units) */
+  int32_t reserved[4];
+} d2pc_sectors_geometry_t;
+/* Host arithmetic only, no device.  The refusals are d2pc_sectors_create's.  D2PC_ERR_INVALID_ARG: NULL, struct_size,
+ * axes, an odd n_sectors or one out of range, a NaN parameter or a non-finite azimuth0, r_min < 0, r_min > r_max,
+ * u_min > u_max, min_count < 1, no_obstacle_cm > 65535.  D2PC_ERR_BAD_SIZE: n_layers out of range; n_layers > 1 with a
+ * non-finite or empty height band, or one so narrow or wide that inv_h is not a positive finite number. */
+int d2pc_sectors_geometry(const d2pc_sectors_config *cfg, d2pc_sectors_geometry_t *out);
+/* Host only: the boundary table, c[j] and s[j] for j < n_sectors / 2.  Returns the number of entries (> 0), or the
+ * negated d2pc_status: of the configuration's refusal, D2PC_ERR_INVALID_ARG for NULL, D2PC_ERR_CAPACITY when
+ * capacity < n_sectors / 2. */
+int d2pc_sectors_table(const d2pc_sectors_config *cfg, float *c, float *s, int capacity);
+
+typedef struct d2pc_sectors d2pc_sectors;
+/* Allocates everything the session will ever need (the table and the blocks' slabs): d2pc_sectors_process_device
+ * allocates nothing.  D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
+int d2pc_sectors_create(const d2pc_sectors_config *cfg, d2pc_sectors **out);
+int d2pc_sectors_destroy(d2pc_sectors *s);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_last_error(const d2pc_sectors *s);
+/* Blocks of the reducing kernel this session launches (0 for NULL); one block walks D2PC_SECTORS_SHARE_POINTS records
+ * per step, block b takes shares b, b + blocks, ... of the call's records. */
+int d2pc_sectors_blocks(const d2pc_sectors *s);
+
+/* The clouds follow d2pc_texture_desc, so every producer plugs in unchanged. */
+typedef struct d2pc_sectors_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_desc) */
+  int32_t point_step;          /* 16 (d2pc_process_device, the rig) or 32 (d2pc_texture_device): bytes of a record */
+  int32_t n_clouds;            /* 1 .. 65,535 */
+  int32_t reserved;            /* zero */
+  const void *points;          /* DEVICE: the records, 16-byte aligned; x, y, z are a record's first three floats */
+  const uint32_t *counts;      /* DEVICE, nullable: records of each cloud (for a rig pass d_offsets + n_cameras with
+                                  n_clouds 1).  NULL = cloud_points each; a count above cloud_points is clamped;
+                                  0xFFFFFFFF (the in-band failure mark of d2pc_process_device) counts as 0 */
+  size_t cloud_points;         /* records one cloud may hold, 1 .. 2^32 - 1 */
+  size_t points_frame_stride_points;  /* records between the clouds in `points` (ignored for one cloud) */
+  float *range;                /* DEVICE out, nullable; at least one of the four is given */
+  uint32_t *count;
+  uint32_t *nearest;
+  uint16_t *distance_cm;
+} d2pc_sectors_desc;
+/* struct_size, point_step 16, n_clouds 1; everything else zero. */
+void d2pc_sectors_desc_init(d2pc_sectors_desc *desc);
+/* Host only: what d2pc_sectors_process_device refuses of `desc` for a session of `cfg`, without a session.
+ * D2PC_ERR_INVALID_ARG: NULL, struct_size, point_step, n_clouds, a NULL `points`, no output, `points` not 16-byte
+ * aligned, counts / an output not aligned to its type, an output that overlaps `points`, `counts` or another output.
+ * D2PC_ERR_BAD_SIZE: cloud_points of 0 or >= 2^32, a frame stride below cloud_points, a largest position
+ * (n_clouds - 1) * stride + cloud_points - 1 at or above 0xFFFFFFFF (that word marks an empty cell). */
+int d2pc_sectors_desc_check(const d2pc_sectors_config *cfg, const d2pc_sectors_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): two launches, no memset, no allocation, no count read on
+ * the host -- it can be captured into a graph as it is, behind its producer.  Every refusal is made before anything
+ * is enqueued.  The result is bit-reproducible: no float is summed and every minimum is of integers.
+ * The slabs belong to the session: one launch of a session in flight per stream order; two streams need two sessions.
+ */
+int d2pc_sectors_process_device(d2pc_sectors *s, const d2pc_sectors_desc *desc, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* D2PC_SECTORS_H */

@@ -1,0 +1,241 @@
+#!/usr/bin/env python3
+"""What the obstacle sectors (include/d2pc_sectors.h) cost behind their producer, interleaved in ONE process on ONE
+device (tools/ab.py's method: the arms take turns round by round; devices and runs differ by ~10 %, so nothing else
+ranks them).  GPU box only.
+
+  A   the producer alone (d2pc_process_device / d2pc_rig_process_device)
+  B   the producer + d2pc_sectors_process_device behind it, on one stream
+  S   d2pc_sectors_process_device alone, on the cloud the producer left (two launches)
+  S0  the same call with every count 0: what the two launches cost before the first record (the blocks' tables are
+      initialised and stored as slabs, the finishing kernel does all of its work)
+  C   d2pc_membench_copy (d2pc_ext.h) that moves as many bytes as S reads (a copy of half of them: read + written), in
+      the same run: what this device gives a kernel that only streams.  There is no earlier time to compare with.
+  CPU tests/sectors_ref.py (numpy, one core) on the first million points of the cloud, per million points
+
+  python tools/sectors_bench.py         ->  profiles/sectors_bench.txt
+  python tools/sectors_bench.py --ab    ->  profiles/sectors_ab.txt: the wave pre-reduction against plain per-lane LDS atomics
+                                            (`make sectors SNAME=wave SDEFS=-DD2PC_SECTORS_FORCE_ROUNDS=2`, `... SNAME=plain
+                                            SDEFS=-DD2PC_SECTORS_FORCE_ROUNDS=0`; the product picks by the grid's size), on a
+                                            cloud in producer order and on the same cloud shuffled, for the smallest and the
+                                            largest grid
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import disparity_to_point_cloud_amd as d2pc  # noqa: E402
+import sectors_ref  # noqa: E402
+
+# (name, cameras, w, h, mode, rig, holes)
+CASES = [("1 x 752x480 u8 COMPACT", 1, 752, 480, d2pc.MODE_COMPACT, False, 0.3),
+         ("16 x 752x480 u8 rig merged COMPACT", 16, 752, 480, d2pc.MODE_COMPACT, True, 0.3),
+         ("16 x 3840x2160 u8 PARITY", 16, 3840, 2160, d2pc.MODE_PARITY, False, 0.0)]
+BORDER = 40
+CPU_POINTS = 1_000_000
+
+
+def timed(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1000.0 / iters   # us per call
+
+
+def fmt(v):
+    return "%8.1f (%7.1f .. %7.1f)" % (float(np.median(v)), min(v), max(v))
+
+
+def yaw(deg):
+    a = np.deg2rad(deg)
+    m = np.eye(4)
+    m[0, 0], m[0, 2], m[2, 0], m[2, 2] = np.cos(a), np.sin(a), -np.sin(a), np.cos(a)   # about the optical frame's y
+    return m
+
+
+def interleaved(arms, rounds, iters):
+    t = [[] for _ in arms]
+    for r in range(rounds):
+        for k in range(len(arms)):
+            k2 = (k + r) % len(arms)   # the order rotates too
+            t[k2].append(timed(arms[k2], iters))
+    return t
+
+
+class Producer:
+    """One case's frames, cloud buffers and the call that fills them."""
+
+    def __init__(self, ctx, n, w, h, rig_case, holes, gen):
+        self.n, self.rig_case = n, rig_case
+        self.frames = torch.randint(8, 256, (n, h, w), generator=gen, device="cuda", dtype=torch.int32).to(torch.uint8)
+        if holes:
+            self.frames[torch.rand((n, h, w), generator=gen, device="cuda") < holes] = 0
+        self.roi_n = d2pc.roi_points(w, h, BORDER)
+        self.cap = n * self.roi_n
+        self.pts = torch.empty((self.cap, 4), dtype=torch.float32, device="cuda")
+        self.counts = torch.zeros(n, dtype=torch.int32, device="cuda")
+        self.offsets = torch.zeros(n + 1, dtype=torch.int32, device="cuda")
+        q = d2pc.make_q()
+        qs = [d2pc.rig_compose_q(yaw(360.0 * f / n), q) for f in range(n)]   # the cameras look all round
+        self.rig = d2pc.RigSession(ctx, n, w, h, d2pc.DTYPE_U8, qs) if rig_case else None
+        self.ctx, self.w, self.h = ctx, w, h
+
+    def __call__(self, s):
+        if self.rig_case:
+            self.rig.process_device(self.frames.data_ptr(), 0.125, self.w, self.h * self.w, self.pts.data_ptr(), None, self.cap,
+                                    self.counts.data_ptr(), self.offsets.data_ptr(), s)
+        else:
+            self.ctx.process_device(self.frames.data_ptr(), d2pc.DTYPE_U8, 0.125, self.w, self.h, self.w, self.h * self.w, self.n,
+                                    self.pts.data_ptr(), None, self.roi_n, self.counts.data_ptr(), s)
+
+    def cloud(self):
+        """What the sectors call gets: (n_clouds, cloud_points, stride, counts pointer)."""
+        if self.rig_case:
+            return 1, self.cap, 0, self.offsets.data_ptr() + 4 * self.n
+        return self.n, self.roi_n, self.roi_n, self.counts.data_ptr()
+
+    def close(self):
+        if self.rig is not None:
+            self.rig.close()
+
+
+def bench(a):
+    prop = torch.cuda.get_device_properties(0)
+    lines = ["# tools/sectors_bench.py --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs, %.0f GiB (one device, one process, ONE run; arms interleaved round by round)" % (
+                 prop.name, prop.multi_processor_count, prop.total_memory / 2**30),
+             "# A = producer alone; B = producer + sectors; S = sectors alone (two launches); S0 = sectors with every count 0;",
+             "# C = d2pc_membench_copy moving the bytes S reads (16 B per point); the default grid: 72 sectors x 1 layer, all four outputs",
+             "# us per call: median (min .. max) over the rounds; a timed window is --iters calls or as many as fill ~30 ms",
+             "# CPU = tests/sectors_ref.py (numpy, one core) on the cloud's first %d points, ms per million points" % CPU_POINTS,
+             "%-36s %10s %8s %-30s %-30s %-30s %-30s %-30s %8s %6s %7s %9s" % (
+                 "case", "points", "MB read", "A", "B", "S", "S0", "C", "B-A", "S/C", "S GB/s", "CPU ms/M")]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    for name, n, w, h, mode, rig_case, holes in (CASES if a.only is None else CASES[a.only:a.only + 1]):
+        with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx, d2pc.Sectors() as sec:
+            prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+            n_clouds, cp, stride, counts_ptr = prod.cloud()
+            out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
+                       count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                       nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                       distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
+            zeros = torch.zeros(n_clouds, dtype=torch.int32, device="cuda")
+
+            def produce():
+                prod(s)
+
+            def sectors():
+                sec.process(prod.pts, cp, n_clouds=n_clouds, counts=counts_ptr, frame_stride_points=stride, stream_ptr=s, **out)
+
+            def empty():
+                sec.process(prod.pts, cp, n_clouds=n_clouds, counts=zeros, frame_stride_points=stride, stream_ptr=s, **out)
+
+            def both():
+                produce()
+                sectors()
+
+            both()
+            torch.cuda.synchronize()
+            ctx.check_async_error()
+            cn = prod.counts.cpu().numpy().view(np.uint32)
+            npts = int(cn.sum())
+            assert int(out["count"].cpu().numpy().view(np.uint32).sum()) <= npts
+            read = 16 * npts
+            half = max(read // 2 // 16 * 16, 16)
+            src = torch.empty(half, dtype=torch.uint8, device="cuda")
+            dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+
+            def copy():
+                ctx.membench_copy(src.data_ptr(), dst.data_ptr(), half, s)
+
+            arms = (produce, both, sectors, empty, copy)
+            for fn in arms:   # warm-up: allocations, code objects
+                fn()
+            torch.cuda.synchronize()
+            iters = int(min(max(a.iters, 30000.0 / timed(both, 5)), 4000))
+            t = interleaved(arms, a.rounds, iters)
+            ctx.check_async_error()
+            # the CPU column: the reference on one core, the cloud's first points
+            m = min(CPU_POINTS, int(cn[0]) if not rig_case else npts)
+            xyz = prod.pts[:m, :3].cpu().numpy()
+            ref = sectors_ref.SectorsRef(sec.cfg, d2pc.sectors_table(sec.cfg), sec.geometry)
+            t0 = time.perf_counter()
+            ref.grid(xyz, np.arange(m))
+            cpu = (time.perf_counter() - t0) * 1e3 / (m / 1e6)
+            prod.close()
+        ma, mb, ms, m0, mc = (float(np.median(x)) for x in t)
+        lines.append("%-36s %10d %8.1f %-30s %-30s %-30s %-30s %-30s %8.1f %6.2f %7.0f %9.0f" % (
+            name, npts, read / 1e6, fmt(t[0]), fmt(t[1]), fmt(t[2]), fmt(t[3]), fmt(t[4]), mb - ma, ms / mc, read / ms / 1e3, cpu))
+        print(lines[-1], flush=True)
+        del prod, src, dst
+        torch.cuda.empty_cache()
+    return lines
+
+
+def ab(a):
+    """The two arms of the in-wave reduction on one cloud, in producer order and shuffled."""
+    prop = torch.cuda.get_device_properties(0)
+    lines = ["# tools/sectors_bench.py --ab --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; arms interleaved round by round)" % (prop.name, prop.multi_processor_count),
+             "# wave = libd2pc_sectors_wave.so (-DD2PC_SECTORS_FORCE_ROUNDS=2: two elected cells per wave, then per-lane LDS atomics);",
+             "# plain = libd2pc_sectors_plain.so (-DD2PC_SECTORS_FORCE_ROUNDS=0: per-lane LDS atomics only).  S alone, us per call: median (min .. max)",
+             "# product = libd2pc_sectors.so: wave up to 72 cells, plain beyond",
+             "%-44s %10s %-30s %-30s %-30s %10s" % ("cloud", "points", "wave", "plain", "product", "plain/wave")]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    name, n, w, h, mode, rig_case, holes = CASES[1]
+    for grid in (dict(), dict(n_sectors=360, n_layers=16, u_min=-40.0, u_max=40.0)):
+        with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx, d2pc.Sectors(variant="wave", **grid) as wave, \
+                d2pc.Sectors(variant="plain", **grid) as plain, d2pc.Sectors(**grid) as product:
+            prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+            prod(s)
+            torch.cuda.synchronize()
+            npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n])
+            ordered = prod.pts[:npts].clone()
+            shuffled = ordered[torch.randperm(npts, generator=gen, device="cuda")].contiguous()
+            outs = [dict(range=torch.empty(wave.n_cells, dtype=torch.float32, device="cuda"),
+                         count=torch.empty(wave.n_cells, dtype=torch.int32, device="cuda")) for _ in range(3)]
+            for label, cloud in (("producer order", ordered), ("shuffled", shuffled)):
+                arms = tuple((lambda sec=sec, o=o: sec.process(cloud, npts, stream_ptr=s, **o)) for sec, o in zip((wave, plain, product), outs))
+                for fn in arms:
+                    fn()
+                torch.cuda.synchronize()
+                assert all(torch.equal(outs[0][k], o[k]) for o in outs[1:] for k in o), "the arms disagree"
+                iters = int(min(max(a.iters, 30000.0 / timed(arms[0], 5)), 4000))
+                t = interleaved(arms, a.rounds, iters)
+                lines.append("%-44s %10d %-30s %-30s %-30s %10.2f" % (
+                    "%d x %d cells, %s" % (wave.cfg.n_sectors, wave.cfg.n_layers, label), npts, fmt(t[0]), fmt(t[1]), fmt(t[2]),
+                    float(np.median(t[1])) / float(np.median(t[0]))))
+                print(lines[-1], flush=True)
+            prod.close()
+    return lines
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--only", type=int, default=None, help="one case only, by its index (a profiler run)")
+    ap.add_argument("--ab", action="store_true", help="the A/B of the in-wave reduction instead of the cost table")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    out = a.out or os.path.join(ROOT, "profiles", "sectors_ab.txt" if a.ab else "sectors_bench.txt")
+    lines = ab(a) if a.ab else bench(a)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", out)
+
+
+if __name__ == "__main__":
+    main()

@@ -788,7 +788,13 @@ def test_tile_fused_compact_kernel_with_more_frames_than_resident_bands(n, h, w)
 def test_tile_fused_compact_kernel_beyond_the_early_look_of_its_placing_words(n, h, w):
     """The pipelined kernel requests the words that place a tile early, into registers sized for images up to 16 tiles across
     (4,096 output columns) and 128 bands (4,096 output rows); beyond either it polls as before.  4500 wide = 18 tiles
-    across, 4300 high = 132 bands, 4176 wide = exactly 16 tiles: all three against the two launches, bitwise, and the oracle."""
+    across, 4300 high = 132 bands, 4176 wide = exactly 16 tiles: all three against the two launches, bitwise, and the oracle.
+
+    What this reaches: the three shapes have 54, 264 and 64 tiles per frame against resident / n = 384 or 256 blocks per
+    frame on a 256-CU device, so the router gives every tile a block of its own.  A block then has no tile in waiting while
+    it filters one: CbEarlyPlace::request and take never run, and every tile is placed by cb_look.  The test holds the
+    one-tile-per-block routing of these sizes to the two launches; the early look itself, either side of its limits and in
+    blocks that do walk tiles, is tests/test_callback_compact_occupancy_gpu.py's (`sixteen`, `seventeen`, `tall`)."""
     from disparity_to_point_cloud_amd.torch_api import DeviceBatch
     rng = np.random.default_rng(h + w)
     imgs = rng.integers(0, 256, size=(n, h, w)).astype(np.uint8)

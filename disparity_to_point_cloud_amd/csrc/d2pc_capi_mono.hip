@@ -126,13 +126,6 @@ int callback_event(d2pc_ctx *ctx, size_t i, hipEvent_t *e) {
   return D2PC_OK;
 }
 
-// Can the tile-fused kernel (median + points per tile) serve this call?  COMPACT: a band of tiles must fit the
-// blocks resident at once (k_callback_bs_compact's hand-off), i.e. ROIs up to 128 x 256 pixels wide.
-bool callback_one_kernel_ok(const d2pc_ctx *ctx, bool compact, const Geom &g) {
-  if (!compact) return true;
-  return ctx->cb_fused_compact >= 1 && (g.roi_w + 255u) / 256u <= kCbMaxTilesX;
-}
-
 }  // namespace
 
 extern "C" int d2pc_process_mono_device(d2pc_ctx *ctx, const void *d_image, int dtype, int width, int height,
@@ -166,18 +159,26 @@ extern "C" int d2pc_process_mono_device(d2pc_ctx *ctx, const void *d_image, int 
   const bool capturing = capture_info(user, nullptr);
   // scratch: the 8-bit frames on a 256-byte pitch
   const size_t kpitch = (size_t(width) + 255) & ~size_t(255), kframe = kpitch * size_t(height);
-  // (the same decisions as below: chunked overlap?  filter + points in one kernel, which needs no filtered frames?)
-  const int want_chunks = ctx->cb_chunks > n_frames ? n_frames : ctx->cb_chunks;
-  const bool will_overlap = want_chunks > 1 && !capturing && (median || bridge16) &&
-                            uint64_t(width) * uint64_t(height) * uint64_t(n_frames) / uint64_t(want_chunks) >= (uint64_t(16) << 20);
-  bool one_kernel = false;
-  if (median && ctx->cb_fused == 1 && !will_overlap) {
+  // chunked overlap?  filter + points in one kernel, which needs no filtered frames?  (d2pc_route.hpp)
+  CallbackCall call{};
+  call.width = width;
+  call.height = height;
+  call.n_frames = n_frames;
+  call.median = median;
+  call.bridge16 = bridge16;
+  call.captured = capturing;
+  call.compact = compact;
+  call.roi_w = gin.roi_w;
+  if (median) {
     MedianArgs probe;
     probe.algo = ctx->median_algo;
     probe.n_frames = uint32_t(n_frames);
     median_roi_only(probe, gin, height);
-    one_kernel = median_uses_bs(probe, median_ksize) && callback_one_kernel_ok(ctx, compact, gin);
+    call.bs_median = median_uses_bs(probe, median_ksize);
   }
+  const CallbackPlan plan = plan_callback(CallbackTuning{ctx->cb_chunks, ctx->cb_fused, ctx->cb_fused_compact}, call);
+  const bool one_kernel = plan.one_kernel, overlap = plan.overlap;
+  const int chunk = plan.chunk;
   // The filtered (and rescaled) frames of the two-launch form live in a scratch buffer that belongs to THIS stream's
   // work: like the compaction state, one per stream in flight, so that double-buffered use of a context on two
   // streams never overwrites another call's filtered frames (advisor, round 2).  A capture takes an existing idle
@@ -190,14 +191,6 @@ extern "C" int d2pc_process_mono_device(d2pc_ctx *ctx, const void *d_image, int 
   }
   void *const d_cb_med = scratch ? scratch->p : nullptr;
   void *const d_cb_cvt = scratch ? scratch->p2 : nullptr;
-  // Few, large chunks: a cross-stream dependency costs ~20 us on this runtime (measured: 16 one-frame chunks of
-  // 4K frames are 19 % SLOWER than running in order, 2 chunks 8 % faster), so the batch is only cut when every
-  // chunk carries well over that in kernel time
-  const uint64_t batch_px = uint64_t(width) * uint64_t(height) * uint64_t(n_frames);
-  int n_chunks = ctx->cb_chunks;
-  if (n_chunks > n_frames) n_chunks = n_frames;
-  const bool overlap = n_chunks > 1 && !capturing && (median || bridge16) && batch_px / uint64_t(n_chunks) >= (uint64_t(16) << 20);
-  const int chunk = overlap ? (n_frames + n_chunks - 1) / n_chunks : n_frames;
   hipStream_t sm = user, sr = user;
   if (overlap) {
     if ((st = callback_streams(ctx)) != D2PC_OK) return st;
@@ -255,16 +248,11 @@ extern "C" int d2pc_process_mono_device(d2pc_ctx *ctx, const void *d_image, int 
         if ((st = fill_q(ctx, a, width)) != D2PC_OK) return st;
         a.qs.w_safe = w_safe_for(ctx, g);
         if (compact) {  // the COMPACT form hands row counts over between the tiles of a band: its own state
-          // Residency.  Both forms of the kernel hand counts over between the tiles of a BAND, and a frame's blocks are
-          // dispatched round-robin over the launch's frames (frame = blockIdx % n_frames): a frame needs tiles_x of its
-          // own blocks resident at once, or no frame ever finishes band 0 (advisor, round 3: from ~385 frames of 752x480
-          // or ~55 frames of 4K every wave spun out its 4-s budget).  A call with more frames than that is cut into
-          // sub-batches of nfc frames with resident / nfc > tiles_x, launched back to back on the same stream (they share
-          // the stream's state buffer: a sub-batch's zeroing kernel runs behind the previous sub-batch's last store).
-          const uint32_t tiles_x = (g.roi_w + 255u) / 256u, tiles_y = (g.roi_n / g.roi_w + 31u) / 32u, tpf = tiles_x * tiles_y;
-          const uint32_t resident = uint32_t(ctx->cu_count * (ctx->cb_pipe_blocks_per_cu < 3 ? ctx->cb_pipe_blocks_per_cu : 3));  // (LDS and registers admit 3 per CU)
-          uint32_t nfc = resident / (tiles_x + 1u);  // (tiles_x <= kCbMaxTilesX = 128 < resident: nfc >= 1 on any device of >= 43 CUs)
-          if (nfc == 0) nfc = 1;
+          // Residency: sub-batches of at most cc.nfc frames, launched back to back on the same stream (d2pc_route.hpp)
+          const uint32_t tiles_x = cb_tiles_x(g.roi_w), tiles_y = cb_tiles_y(g.roi_n / g.roi_w);  // (ROI rows)
+          const CallbackCompactPlan cc =
+              plan_callback_compact(ctx->cu_count, ctx->cb_pipe_blocks_per_cu, ctx->cb_fused_compact, tiles_x, tiles_y, uint32_t(nf));
+          const uint32_t nfc = cc.nfc;
           for (int s0 = 0; s0 < nf; s0 += int(nfc)) {
             const int ns = nf - s0 < int(nfc) ? nf - s0 : int(nfc);
             Geom gs;
@@ -289,18 +277,11 @@ extern "C" int d2pc_process_mono_device(d2pc_ctx *ctx, const void *d_image, int 
             sb->hdr_off = 0;
             as.geom = gs;
             as.compact_algo = 1;
-            if (ctx->cb_fused_compact == 2) {
-              // persistent blocks, a multiple of the frame count; every frame needs more blocks than a band has tiles
-              // (or as many as it has tiles): otherwise the one-tile-per-block form serves the launch
-              uint32_t per_frame = resident / uint32_t(ns);
-              if (per_frame > tpf) per_frame = tpf;
-              if (per_frame > tiles_x || per_frame == tpf) {
-                as.grid = per_frame * uint32_t(ns);
-                as.compact_algo = 2;
-              }
+            const CallbackCompactPlan::Sub sub = cc.sub(uint32_t(ns));
+            if (sub.pipelined) {  // (the one-tile-per-block form takes its grid from the launch's own tiles)
+              as.grid = sub.grid;
+              as.compact_algo = 2;
             }
-            // (the one-tile-per-block form: ns * tiles_x <= resident - ns by the choice of nfc, so every frame has a whole
-            // band of blocks resident from the first dispatch round on)
             D2PC_HIP(ctx, launch_callback_bs_compact(as, ms, static_cast<const uint8_t *>(kin) + size_t(s0) * kin_frame, median_ksize));
             if (!sb->captured) sb->dirty = true;
           }

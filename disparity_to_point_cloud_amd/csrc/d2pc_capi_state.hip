@@ -187,6 +187,52 @@ int acquire_buf(d2pc_ctx *ctx, BufPool &pool, hipStream_t stream, size_t need, s
   return D2PC_OK;
 }
 
+// The epoch of the next launch of resident blocks (compact_algo 3); once in 2^30 launches every state buffer of the
+// context starts over from clean state.
+int take_epoch(d2pc_ctx *ctx, uint32_t *epoch) {
+  *epoch = ctx->resident_epoch++;
+  if (ctx->resident_epoch >= kEpochEnd) {  // (once in 2^30 launches: start over from clean state)
+    std::vector<StateBuf *> all(ctx->states.bufs);
+    for (PipeSlot &sl : ctx->slots) all.push_back(&sl.st);  // the pipeline slots' own state buffers carry epochs too
+    for (StateBuf *b : all)
+      if (b->p) {
+        if (!settle(*b)) return fail(ctx, D2PC_ERR_DEVICE, "epoch wrap-around while a stream that uses the context is being captured");
+        if (b->pending) D2PC_HIP(ctx, hipEventSynchronize(b->done));
+        b->pending = false;
+        D2PC_HIP(ctx, hipMemsetAsync(b->p, 0, b->cap, nullptr));
+        D2PC_HIP(ctx, hipStreamSynchronize(nullptr));
+      }
+    ctx->resident_epoch = kEpochBase;  // (only now: a failure above leaves the counter past the end and the next launch tries again)
+  }
+  return D2PC_OK;
+}
+
+// Points the launch at its state in `sb` (acquired with state_need bytes).  The dense single pass cleans up for its
+// successor: it runs on one half of the buffer and zeroes the other (see StateBuf::pp_*); every other launch takes the
+// buffer from its start and leaves no clean half behind.
+void bind_state(StateBuf &sb, LaunchArgs &a, bool self_clean) {
+  a.state = sb.p;
+  if (!self_clean) {
+    sb.pp_clean = false;
+    sb.hdr_off = 0;
+    return;
+  }
+  const size_t half = state_half(a.state_bytes);
+  // clean iff the previous launch's kernel zeroed at least the bytes this one uses, at the same offset (the kernel zeroes
+  // `state_bytes`, not the half rounded up: a smaller predecessor leaves a dirty tail; advisor, round 5)
+  const bool clean = sb.pp_clean && sb.pp_half == half && sb.pp_bytes >= a.state_bytes && !sb.captured;
+  const int h = clean ? sb.pp_next : 0;
+  a.state = static_cast<uint8_t *>(sb.p) + size_t(h) * half;
+  a.state_is_clean = clean;
+  // a captured launch replays on the half baked into it: it keeps the clear kernel in front and cleans nothing
+  a.state_other = sb.captured ? nullptr : static_cast<uint8_t *>(sb.p) + size_t(h ^ 1) * half;
+  sb.pp_half = half;
+  sb.pp_bytes = a.state_bytes;
+  sb.pp_next = h ^ 1;
+  sb.pp_clean = !sb.captured;
+  sb.hdr_off = size_t(h) * half;
+}
+
 // d2pc_reserve / d2pc_reserve_mono: ONE idle buffer of the pool that no graph owns, of at least this size
 int reserve_buf(d2pc_ctx *ctx, BufPool &pool, size_t need, size_t need2) {
   if (need > pool.reserve) pool.reserve = need;
@@ -234,7 +280,7 @@ int d2pc_reserve(d2pc_ctx *ctx, int width, int height, int n_frames) {
   // Guarantees ONE free (idle, not owned by a captured graph) buffer of this size, and makes it the
   // minimum size of every buffer allocated later.  Call it before each capture that contains a COMPACT launch.
   // (twice: the dense single pass keeps two states per buffer -- one in use, one it cleans for its successor)
-  return reserve_buf(ctx, ctx->states, 2 * ((compact_state_bytes(g) + 255) & ~size_t(255)), 0);
+  return reserve_buf(ctx, ctx->states, state_need(compact_state_bytes(g), true), 0);
 }
 
 int d2pc_reserve_mono(d2pc_ctx *ctx, int dtype, int width, int height, int n_frames) {
@@ -250,8 +296,8 @@ int d2pc_reserve_mono(d2pc_ctx *ctx, int dtype, int width, int height, int n_fra
   if (ctx->cfg.mode != D2PC_MODE_COMPACT) return D2PC_OK;
   // COMPACT: the state of the two-launch form's compaction and of the tile-fused kernel, whichever is larger
   const long long b = ctx->cfg.border, rw = (long long)width - 2 * b, rh = (long long)height - 2 * b;
-  if (rw > 0 && rh > 0 && (rw + 255) / 256 <= (long long)kCbMaxTilesX) {
-    const size_t cb = callback_compact_state_bytes(uint32_t((rw + 255) / 256), uint32_t((rh + 31) / 32), uint32_t(n_frames), nullptr);
+  if (rw > 0 && rh > 0 && cb_tiles_x(uint32_t(rw)) <= kCbMaxTilesX) {
+    const size_t cb = callback_compact_state_bytes(cb_tiles_x(uint32_t(rw)), cb_tiles_y(uint32_t(rh)), uint32_t(n_frames), nullptr);
     if (cb > ctx->states.reserve) ctx->states.reserve = cb;
   }
   return d2pc_reserve(ctx, width, height, n_frames);

@@ -1,15 +1,17 @@
 // d2pc_ctx.hpp -- the device context behind include/d2pc.h and what the d2pc_capi_*.hip translation units share.
 // Host code only (no kernel here): the C ABI was one 2,200-line file until round 6; it is now cut along its seams --
 //   d2pc_capi_context.hip  status strings, calibration (Q, blob, closed forms), create / destroy, fill_q / classify_q
-//   d2pc_capi_state.hip    the pool of per-stream state buffers (lazy events, captures, self-cleaning halves), d2pc_reserve*,
-//                          d2pc_check_async_error, d2pc_compact_stats
-//   d2pc_capi_route.hip    launch geometry and the routing of one device-resident call (enqueue), d2pc_process_device
+//   d2pc_capi_state.hip    the pool of per-stream state buffers (lazy events, captures, self-cleaning halves, the resident
+//                          launches' epochs), d2pc_reserve*, d2pc_check_async_error, d2pc_compact_stats
+//   d2pc_capi_route.hip    launch geometry and one device-resident call carried out to its plan (enqueue), d2pc_process_device
 //   d2pc_capi_host.hip     the synchronous host entry points (d2pc_process*) and the pipelined host path (d2pc_pipeline_*)
 //   d2pc_capi_mono.hip     cv_bridge rescale, median, the device-resident callback body (d2pc_process_mono_device)
 //   d2pc_capi_fusion.hip   depth-map fusion inner loop, rotate, crop
 //   d2pc_capi_node.hip     the depth_map_fusion node as a session (d2pc_fusion_node_*)
 //   d2pc_capi_rig.hip      a camera rig as a session (d2pc_rig_*: n cameras, n Qs in a device table, one merged cloud; d2pc_rig.hpp)
 //   d2pc_capi_ext.hip      include/d2pc_ext.h: tuning keys, test hooks, device calibration kernels
+//   d2pc_route.hpp         the launch plans: which kernel serves a COMPACT call or a callback body, in which tile shape and grid
+//                          (plan_compact, plan_callback, plan_callback_compact) and every threshold they turn on; no HIP
 //   d2pc_plane.hpp         one image plane (pointer, pitch, frame stride, rows x row bytes): fit, extent, overlap; no HIP.
 //                          Which rule each image entry point passes to Plane::fits (d2pc_process* have make_geom's own):
 //     d2pc_fuse_device, d2pc_score_filter_device         Bound32::Plane (pitch * rows < 2^32), FrameRule::LastRow
@@ -37,6 +39,7 @@
 #include "d2pc_device.hpp"
 #include "d2pc_launch.hpp"
 #include "d2pc_plane.hpp"
+#include "d2pc_route.hpp"
 
 using namespace d2pc;  // (host translation units of the library only)
 
@@ -116,16 +119,16 @@ struct d2pc_ctx {
   QStereo qs{};
   // tuning (d2pc_set_tuning); defaults from tools/ab.py sweeps on MI355X
   // (fast and slow devices agree on 2048-pixel tiles and 2-4 tiles per block)
-  int pxt_parity = 0, pxt_compact = 8;  // ROI pixels per thread; parity 0 = choose per launch (parity_pxt below)
+  int pxt_parity = 0, pxt_compact = 8;  // ROI pixels per thread; parity 0 = choose per launch (parity_pxt, d2pc_route.hpp)
   int parity_small = 0;          // PARITY kernel form: 0 = choose, 1 = one-shot blocks of 256 * pxt pixels (pxt 1, 2, 4), 2 = tiles walked by fewer blocks
   int blocks_per_cu = 128;
   int onepass_blocks_per_cu = 0;   // resident 5-wave blocks per CU (73 VGPRs, 33 KB LDS each: 4 fit); 0 = choose per launch
-  int onepass_form = 0;            // which single-pass kernel: 0 = choose (kDefaultOnepassForm), 1 / 2 / 3: see enqueue
+  int onepass_form = 0;            // which single-pass kernel: 0 = choose (kDefaultOnepassForm), 1 / 2 / 3: see plan_compact
 #if D2PC_EXPERIMENTS
   int big_batch_algo = 2;          // COMPACT launches of >= 4 frames and >= 20,480 tiles: 2 = single pass (default: faster), 4 = chunked two-pass of one-shot blocks
   int chunk_mb = 96;               // algo 4: input bytes per chunk (MiB); the chunk must stay in the 256 MiB Infinity Cache for one launch
   int chunk_first_frames = 0;      // algo 4: frames of the first chunk (0 = an eighth of a chunk)
-  int resident_unbounded = 0;      // algo 3: admit launches of more blocks than are resident at once (see enqueue)
+  int resident_unbounded = 0;      // algo 3: admit launches of more blocks than are resident at once (see resident_fit)
   int general_q_form = 0;          // 0: OpenCV 3/4's association bit for bit; 1: fused multiply-adds (round 2's form)
   // closed experiments (round 6: behind the experiment build; the product runs their measured defaults)
   int resident_stagger_pct = -1;   // algo 3, register-resident form: scale of the ramped start in % (0 = every block loads at once;
@@ -196,8 +199,6 @@ struct d2pc_ctx {
 namespace d2pc {
 namespace host {
 
-constexpr int kDefaultOnepassForm = 2;  // profiles/r05_ab_onepass_forms_*.txt: never slower than form 1, 5-6 % faster with 30 % holes, 29 % with 90 %
-
 // records the message in the context, returns `status` (d2pc_last_error)
 int fail(d2pc_ctx *ctx, int status, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
 
@@ -254,6 +255,11 @@ int eager_bufs(const BufPool &pool);
 int acquire_buf(d2pc_ctx *ctx, BufPool &pool, hipStream_t stream, size_t need, size_t need2, StateBuf *fixed, StateBuf **out);
 int reserve_buf(d2pc_ctx *ctx, BufPool &pool, size_t need, size_t need2);
 void free_pool(BufPool &pool);
+int take_epoch(d2pc_ctx *ctx, uint32_t *epoch);
+// state bytes of one launch in its buffer: the dense single pass keeps two states, each rounded up to 256 bytes
+inline size_t state_half(size_t state_bytes) { return (state_bytes + 255) & ~size_t(255); }
+inline size_t state_need(size_t state_bytes, bool self_clean) { return self_clean ? 2 * state_half(state_bytes) : state_bytes; }
+void bind_state(StateBuf &sb, LaunchArgs &a, bool self_clean);
 
 // ---- d2pc_capi_context.hip -------------------------------------------------------------------------------------------
 int fill_q(d2pc_ctx *ctx, LaunchArgs &a, int width);

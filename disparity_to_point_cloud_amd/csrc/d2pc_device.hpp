@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "d2pc_route.hpp"  // kBlock, kCbMaxTilesX, kResidentBlocksPerCu: the routing constants and what interprets them
+
 // The shipped library holds the product's kernels only.  -DD2PC_EXPERIMENTS=1 (libd2pc_exp.so; `make exp`) adds the
 // laboratory: tile shapes other than the defaults, the tile-walking PARITY kernel of rounds 1-2, the chunked two-pass
 // (compact_algo 4), the register-resident form over more blocks than are resident, round 2's fused general-Q form.
@@ -21,8 +23,6 @@
 #endif
 
 namespace d2pc {
-
-constexpr int kBlock = 256;  // threads per workgroup (4 waves of 64)
 
 // ---- exact unsigned division by a launch-time constant --------------------
 // Granlund-Montgomery round-up method: q = (t + ((n - t) >> s1)) >> s2 with
@@ -164,11 +164,9 @@ struct CompactStats {
 // tile-fused COMPACT callback kernel (k_callback_bs_compact): per frame [ticket, 128 B][band accumulators, 8 B
 // each, rounded up to 128 B][64 B of row counts per tile]
 constexpr uint32_t kCbTicketBytes = 128;
-constexpr uint32_t kCbMaxTilesX = 128;  // tiles per band: far below the blocks resident at once (3 per CU)
 __host__ __device__ inline uint32_t cb_band_acc_bytes(uint32_t tiles_y) { return (tiles_y * 8u + 127u) & ~127u; }
 // compact_algo 3 (k_compact_resident): the launch epochs its granules carry instead of being zeroed
 constexpr uint32_t kEpochBase = 1u << 30, kEpochEnd = 1u << 31;
-constexpr int kResidentBlocksPerCu = 4;  // what k_compact_resident's grid may be at most, per CU (<= 128 VGPRs: admitted)
 constexpr uint32_t kFrameTicketBytes = 256;   // the ticket word has a 256-B block to itself
 constexpr uint32_t kGroupAccStride = 128;     // one group accumulator per 128-B line
 constexpr uint64_t kGranuleTag = uint64_t(1) << 63;

@@ -54,12 +54,11 @@ import callback_patterns as cp
 import disparity_to_point_cloud_amd as d2pc
 import oracle
 from helpers import assert_points_close
+from route_model import CU_DEFAULT, PIPE_BLOCKS_PER_CU_DEFAULT, callback_route
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-CU_DEFAULT = 256                 # an MI355X; the GPU tests read the device's own count
-PIPE_BLOCKS_PER_CU_DEFAULT = 3
 PT_SENTINEL, IX_SENTINEL = 0x7FC5A5A5, 0x5A5AA5A5   # a NaN with a payload no kernel produces; an index beyond any batch here
 # Scales at which every non-zero byte decodes to a sliver W (table class 2: a block then takes the exact path for good).
 # 1.3e-41 is the degenerate-scale test's: Z = f / W overflows for every byte, nothing survives.  At 3e-39 W = q32 * d lies
@@ -81,7 +80,6 @@ GENERATORS_ON = {"five": cp.GENERATORS, "five_odd": ("row_counts", "edges"), "fi
                  "taller": ("tile_ramp", "empty_bands"), "taller2": ("tile_ramp", "empty_bands"), "small3": ("row_counts", "edges")}
 
 Case = namedtuple("Case", "routing generator k general_q holes scale part")
-Route = namedtuple("Route", "n resident nfc per_frame tiles_x tiles_y tpf sub_batches pipelined")
 
 
 def case_id(c):
@@ -127,20 +125,11 @@ def frame_order(case, n):
     return [f % len(p.frames) for f in range(n)]
 
 
-# ------------------------------------------------------------------------------------------------------- the router, restated
+# ----------------------------------------------------------------------------------------- the router, restated in route_model
 def route(routing, cu=CU_DEFAULT):
-    """d2pc_capi_mono.hip's residency rule for the fused COMPACT forms: -> Route.  n is chosen from the CU count so that a
-    steady-state case gets about the per_frame it aims at."""
+    """The residency rule for the fused COMPACT forms (route_model.callback_route) on a routing of ROUTINGS: -> Route."""
     shape, per_cu, aim = ROUTINGS[routing]
-    roi_w, roi_h = cp.SHAPES[shape]
-    tiles_x, tiles_y = cp.tiles(roi_w, roi_h)
-    tpf = tiles_x * tiles_y
-    n = cu // aim if aim else 3
-    resident = cu * min(per_cu, 3)
-    nfc = max(resident // (tiles_x + 1), 1)
-    ns = min(n, nfc)                                        # the first sub-batch
-    per_frame = min(resident // ns, tpf)
-    return Route(n, resident, nfc, per_frame, tiles_x, tiles_y, tpf, -(-n // nfc), per_frame > tiles_x or per_frame == tpf)
+    return callback_route(*cp.SHAPES[shape], per_cu, aim, cu)
 
 
 def assert_steady(r, what):

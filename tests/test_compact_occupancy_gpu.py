@@ -34,13 +34,11 @@ import disparity_to_point_cloud_amd as d2pc
 import occupancy_patterns as op
 import oracle
 from helpers import check_compact_is_filtered_parity
+from route_model import BIG_BATCH_TILES, route     # the router, restated: compared with the C++ on a CPU by test_route_plan_cpu.py
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
-CU_DEFAULT = 256                   # an MI355X; the GPU tests read the device's own count
-RESIDENT_BLOCKS_PER_CU = 4
-BIG_BATCH_TILES = 20480
 PT_SENTINEL, IX_SENTINEL = 0x7FC5A5A5, 0x5A5AA5A5   # a NaN with a payload no kernel produces; an index beyond any frame
 
 CASES = {2048: op.make_cases(2048), 1024: op.make_cases(1024, thin=True), 4096: op.make_cases(4096, thin=True)}
@@ -104,32 +102,6 @@ def case_of(tile, name):
         if c.name == name:
             return c
     raise AssertionError(f"{name}@{tile} is not a case of CASES: its reach is asserted nowhere")
-
-
-# ------------------------------------------------------------------------------------------------------- the router, restated
-def tiles_of(roi_n, pxt):
-    return -(-roi_n // (256 * pxt))
-
-
-def route(algo, roi_n, n_frames, pxt=8, resident_pxt=0, onepass_form=0, cu=CU_DEFAULT):
-    """-> (serving algorithm, its pixels per thread, its tiles per launch): d2pc_capi_route.hip's enqueue for an eager
-    launch of >= 3 frames or a forced algorithm (the two-frame split of algo 0 / 3 is not used here)."""
-    cap = cu * RESIDENT_BLOCKS_PER_CU
-    big = n_frames >= 4 and tiles_of(roi_n, pxt) * n_frames >= BIG_BATCH_TILES
-    fits = lambda r: tiles_of(roi_n, r) * n_frames <= cap and tiles_of(roi_n, r) <= 1024   # noqa: E731
-    rp = next((r for r in (pxt, 32, 64) if fits(r)), 0)
-    if resident_pxt:
-        rp = resident_pxt if fits(resident_pxt) else 0
-    a = algo or (2 if big else 3 if rp else 1)
-    if a == 3 and not rp:
-        a = 2 if big else 1
-    if a == 2:
-        form = onepass_form or 2
-        fp = 16 if form in (3, 5, 7) else 8 if form >= 2 else pxt
-        return 2, fp, tiles_of(roi_n, fp) * n_frames
-    if a == 3:
-        return 3, rp, tiles_of(roi_n, rp) * n_frames
-    return a, pxt, tiles_of(roi_n, pxt) * n_frames
 
 
 # --------------------------------------------------------------------------------------------------------------- contexts

@@ -599,6 +599,39 @@ def test_c4_4k_compact_frames_take_one_launch_each(n, pair):
         assert_points_close(pts, wp, max_ulp=1, rel=1e-5, what=f"4K compact frame {f}")
 
 
+@pytest.mark.parametrize("kind", ["uniform", "holes"])
+@pytest.mark.parametrize("side", ["below", "above"])
+def test_two_frame_call_either_side_of_the_split_s_seam(side, kind):
+    """Two frames whose pair just fits the resident blocks at 32 pixels per thread (2,048 x 2 cap pixels each, cap = 4 per
+    CU: 2 x cap / 2 blocks) go as ONE launch; one row more per frame (2 x (cap / 2 + 1) blocks) and the call is split
+    into two launches of one frame each.  Frame sizes, launches and tiles from tests/route_model.py on the device's own
+    CU count; default routing, no hook, no tuning; bytes against the oracle in OpenCV 2.4's form."""
+    import route_model as rm
+    cu = torch.cuda.get_device_properties(0).multi_processor_count
+    cap = cu * rm.RESIDENT_BLOCKS_PER_CU
+    w, h = 2048, 2 * cap + (side == "above")
+    plan = rm.compact_plan(0, w * h, 2, cu=cu)
+    assert plan.split == (side == "above") and (plan.split or (plan.algo, plan.pxt, plan.tiles) == (3, 32, cap)), plan
+    one = rm.compact_plan(0, w * h, 1, cu=cu)         # what each launch of a split call gets
+    assert one.algo == 3 and not one.split and (side == "below" or (one.pxt, one.tiles) == (32, cap // 2 + 1)), one
+    launches, tiles = (2, 2 * one.tiles) if plan.split else (1, plan.tiles)
+    q = d2pc.make_q()
+    frames = [synth_disparity(4, 50 + f, w, h, kind) for f in range(2)]
+    with d2pc.Context(q=q, border=0, mode=d2pc.MODE_COMPACT) as ctx:
+        ctx.set_reproject_form(d2pc.FORM_CV24)
+        b = _batch(ctx, frames, want_index=True)
+        ctx.compact_stats_reset()
+        b.launch()
+        res = b.results()
+        ctx.check_async_error()
+        st = ctx.compact_stats()
+    assert (st["launches"], st["tiles"], st["timeouts"], st["twopass_fallbacks"]) == (launches, tiles, 0, 0), (st, plan, one)
+    for f, (pts, idx) in enumerate(res):
+        wp, wi = oracle.reproject_compact(frames[f], q, border=0, form=oracle.FORM_CV24)
+        assert np.array_equal(idx, wi), f"frame {f} indices"
+        assert np.array_equal(pts.view(np.uint32), wp.view(np.uint32)), f"frame {f} points"
+
+
 def test_a_give_up_in_the_first_frame_of_a_two_frame_call_is_reported():
     """Advisor, round 5 (medium): two 4K frames in one COMPACT call are TWO resident launches with consecutive epochs on one
     state buffer.  A hand-off give-up in frame 0's launch stores epoch E in the header while the buffer remembered only E + 1:

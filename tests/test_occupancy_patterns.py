@@ -9,7 +9,8 @@ import pytest
 
 import occupancy_patterns as op
 import oracle
-from test_compact_occupancy_gpu import CASES, LADDER, PATTERN_TESTS, paths_for, route
+from route_model import route
+from test_compact_occupancy_gpu import CASES, LADDER, PATTERN_TESTS, paths_for
 
 import disparity_to_point_cloud_amd as d2pc
 

@@ -21,7 +21,12 @@
 //     d2pc_fusion_node_callback_device (incoming frame)  Bound32::Pitch, FrameRule::LastRow
 //     d2pc_rig_process_device (the cameras' frames)      Bound32::Plane, FrameRule::LastRow, behind make_geom's own rules
 //     d2pc_texture_device (the texture; d2pc_capi_rig.hip) Bound32::Pitch, FrameRule::LastRow; 16- / 32-bit samples aligned
-// Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol).
+// The kernels behind d2pc_launch.hpp are one file per mode or filter beside these; the closed experiments' kernels are
+// lab/*.hip, which only the builds with -DD2PC_EXPERIMENTS=1 compile (the Makefile's LAB_SRCS) and which the product's
+// sources reach through the *_lab hooks of d2pc_launch.hpp alone (tests/test_abi_cpu.py holds that rule).
+// Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol), and nothing
+// else is exported: d2pc.map keeps d2pc::host::*, d2pc::launch_* and the kernel handles inside the library, since the
+// flavours define those names over different layouts of d2pc_ctx (::test_library_exports_nothing_undeclared).
 #pragma once
 #include <hip/hip_runtime.h>
 

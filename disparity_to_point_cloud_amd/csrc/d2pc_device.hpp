@@ -17,7 +17,9 @@
 // The shipped library holds the product's kernels only.  -DD2PC_EXPERIMENTS=1 (libd2pc_exp.so; `make exp`) adds the
 // laboratory: tile shapes other than the defaults, the tile-walking PARITY kernel of rounds 1-2, the chunked two-pass
 // (compact_algo 4), the register-resident form over more blocks than are resident, round 2's fused general-Q form.
-// tests/ and tools/ that exercise those load the experiment build; nothing in include/d2pc.h refers to them.
+// tests/ and tools/ that exercise those load the experiment build; nothing in include/d2pc.h refers to them.  The
+// laboratory's own kernels and launchers are lab/*.hip; in the product's sources the macro guards hooks, limits and
+// instantiations of product templates, never a definition.
 #ifndef D2PC_EXPERIMENTS
 #define D2PC_EXPERIMENTS 0
 #endif

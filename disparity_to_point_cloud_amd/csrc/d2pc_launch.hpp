@@ -162,10 +162,16 @@ hipError_t launch_parity(const LaunchArgs &a);          // d2pc_parity.hip
 hipError_t launch_onepass(const LaunchArgs &a);         // d2pc_onepass.hip (compact_algo 2: state clear + single pass)
 // zeroes a compaction state buffer and starts its header (d2pc_onepass.hip); also ahead of the tile-fused COMPACT callback kernels
 hipError_t launch_state_clear(void *state, size_t state_bytes, void *stats, hipStream_t stream, bool keep_timeout = false);
-// experiment build only (d2pc_chunk.hip, compact_algo 4): bytes of state per frame for frames of `tiles_per_frame`
-// 512-pixel tiles, and the words its group totals take
+#if D2PC_EXPERIMENTS  // the laboratory's launchers (lab/*.hip): what the product's launchers hand over to in the experiment build
+hipError_t launch_parity_lab(const LaunchArgs &a);                  // lab/d2pc_parity_lab.hip: the tile-walking kernel (pxt 4 / 8 / 16)
+hipError_t launch_onepass_lab(const LaunchArgs &a, uint32_t grid);  // lab/d2pc_onepass_lab.hip: onepass_form 1 and 4; state cleared, grid in whole frames
+// lab/d2pc_median_bs2.hip (median_algo 3): a.tiles_* filled, `blocks` = tiles of all frames
+hipError_t launch_median_bs2(const uint8_t *src, uint8_t *dst, const MedianArgs &a, int ksize, uint32_t blocks, hipStream_t stream);
+// lab/d2pc_chunk.hip (compact_algo 4): bytes of state per frame for frames of `tiles_per_frame` 512-pixel tiles, and the
+// words its group totals take
 uint32_t chunk_frame_state_stride(uint32_t tiles_per_frame, uint32_t *gsum_words);
 hipError_t launch_compact_chunked(const LaunchArgs &a);
+#endif
 // tile-fused callback body (bit-sliced k x k median + PARITY reprojection of the tile from LDS;
 // k_callback_bs): `m` carries the filter's geometry with the output rectangle = the ROI of a.geom; a.out_points,
 // a.out_index (nullable), a.counts (nullable), a.q*, a.stream as in launch_parity

@@ -1,9 +1,8 @@
-// d2pc_chunk.hip -- EXPERIMENT BUILD ONLY (-DD2PC_EXPERIMENTS=1): the chunked two-pass compaction of round 4
+// lab/d2pc_chunk.hip -- EXPERIMENT BUILD ONLY (-DD2PC_EXPERIMENTS=1): the chunked two-pass compaction of round 4
 // (compact_algo 4).  Bit-identical to the other COMPACT forms and 15-25 % slower than the single pass on every big
 // batch measured (profiles/r04_ab_chunked.txt); kept as a recorded negative that tests and tools can still run.
-#include "d2pc_compact_common.hpp"
+#include "../d2pc_compact_common.hpp"
 
-#if D2PC_EXPERIMENTS
 namespace d2pc {
 
 // --------------------------------------------------------------------------
@@ -369,4 +368,3 @@ uint32_t chunk_frame_state_stride(uint32_t tiles_per_frame, uint32_t *gsum_words
 
 
 }  // namespace d2pc
-#endif  // D2PC_EXPERIMENTS

@@ -120,7 +120,7 @@ int d2pc_last_stage_times(d2pc_ctx *ctx, d2pc_stage_times *times);
  * launch each (the product), 1 = round 4's one launch of blocks twice the size -- and "resident_stagger_pct", the scale of
  * the resident blocks' ramped start: profiles/r04_ab_stagger.txt, r05_ab_pair.txt.)
  *
- * EXPERIMENT BUILD (libd2pc_exp.so = the same sources with -DD2PC_EXPERIMENTS=1, `make -C csrc exp`; what tests/ and
+ * EXPERIMENT BUILD (libd2pc_exp.so = the same sources + csrc/lab/ with -DD2PC_EXPERIMENTS=1, `make -C csrc exp`; what tests/ and
  * tools/ load to re-run recorded negatives; never shipped, never what INTEGRATION.md links).  It adds, and only it
  * accepts: d2pc_config.compact_algo = 4 (round 4's two-pass over Infinity-Cache-sized pieces of the batch, 15-25 % slower
  * than the single pass: docs/HISTORY.md) with its keys "big_batch_algo" (2 / 4: what compact_algo 0 takes for big

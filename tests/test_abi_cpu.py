@@ -32,14 +32,119 @@ def test_library_exports_every_declared_symbol():
     assert sorted(capi.EXT_SYMBOLS) == ext, "python binding and d2pc_ext.h disagree"
 
 
-def test_library_exports_nothing_undeclared():
-    """Every d2pc_* symbol the shared object exports is declared in one of the two headers (no hidden surface)."""
+def _dynamic_symbols(so):
+    """Every defined dynamic symbol of a shared object, whatever its type or name."""
     import subprocess
-    so = os.path.join(ROOT, "disparity_to_point_cloud_amd", "libd2pc.so")
     out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    exported = sorted({ln.split()[-1] for ln in out.splitlines() if ln.split() and ln.split()[-1].startswith("d2pc_")
-                       and ln.split()[-2] in ("T", "W")})
-    assert exported == sorted(_header_functions("d2pc.h") + _header_functions("d2pc_ext.h"))
+    return sorted({ln.split()[-1] for ln in out.splitlines() if ln.split()})
+
+
+def test_library_exports_nothing_undeclared():
+    """EVERY defined dynamic symbol of the shared objects is declared in a header (csrc/d2pc.map): no kernel handle, no
+    d2pc::host::* or d2pc::launch_* -- the two flavours define those names over different `struct d2pc_ctx` layouts."""
+    pkg = os.path.join(ROOT, "disparity_to_point_cloud_amd")
+    declared = sorted(capi.ABI_SYMBOLS + capi.EXT_SYMBOLS)
+    assert declared == sorted(_header_functions("d2pc.h") + _header_functions("d2pc_ext.h"))
+    assert _dynamic_symbols(os.path.join(pkg, "libd2pc.so")) == declared
+    if os.path.exists(capi.library_path("exp")):
+        assert _dynamic_symbols(capi.library_path("exp")) == declared
+    sectors = _header_functions("d2pc_sectors.h")
+    exported = _dynamic_symbols(os.path.join(pkg, "libd2pc_sectors.so"))
+    assert exported and set(exported) <= set(sectors), sorted(set(exported) - set(sectors))
+
+
+CSRC = os.path.join(ROOT, "disparity_to_point_cloud_amd", "csrc")
+GUARD_EXEMPT = ("d2pc_ctx.hpp", "d2pc_capi_ext.hip", "d2pc_capi_route.hip")   # host-side state, keys and routing of the laboratory
+
+
+def _make_list(name):
+    """The words of `name := ...` in csrc/Makefile (continuation lines joined)."""
+    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
+    m = re.search(r"^%s\s*:=(.*)$" % name, text, flags=re.M)
+    assert m, name
+    return m.group(1).split()
+
+
+def _csrc_files(*suffixes):
+    return sorted(os.path.relpath(os.path.join(d, f), CSRC) for d, _, fs in os.walk(CSRC) for f in fs
+                  if f.endswith(suffixes) and not os.path.relpath(d, CSRC).startswith("build"))
+
+
+def test_makefile_names_every_source_once_and_ros_builds_through_it():
+    """One list of sources: every .hip under csrc/ is in exactly one of the Makefile's product, laboratory or sectors
+    lists, the product's list reaches into lab/ nowhere, and ros/CMakeLists.txt names paths that exist and no source."""
+    import glob
+    product, lab, sectors = _make_list("SRCS"), _make_list("LAB_SRCS"), _make_list("SECTORS_SRCS")
+    assert sorted(product + lab + sectors) == _csrc_files(".hip")            # (equal as lists: nothing missing, nothing twice)
+    assert lab and all(f.startswith("lab/") for f in lab + _make_list("LAB_HDRS"))
+    assert not [f for f in product + _make_list("HDRS") + sectors + _make_list("SECTORS_HDRS") if "lab/" in f]
+    for f in _make_list("HDRS") + _make_list("LAB_HDRS") + _make_list("SECTORS_HDRS"):
+        assert os.path.isfile(os.path.join(CSRC, f)), f
+    cm = open(os.path.join(ROOT, "ros", "CMakeLists.txt")).read()
+    cm = re.sub(r"#.*", "", cm)
+    assert ".hip" not in cm.replace("*.hip", ""), "ros/CMakeLists.txt keeps a source list of its own"
+    where = {"D2PC_ROOT": ROOT, "D2PC_CSRC": CSRC}
+    paths = re.findall(r"\$\{(D2PC_ROOT|D2PC_CSRC)\}(/[^\s\")]+)", cm)
+    assert len(paths) >= 6
+    for var, rest in paths:
+        assert glob.glob(where[var] + rest), "${%s}%s" % (var, rest)
+
+
+def _split_guarded(text):
+    """The lines of `text` between an `#if D2PC_EXPERIMENTS` and its #endif (nested conditionals followed), and the rest."""
+    inside, outside, depth = [], [], 0
+    for ln in text.splitlines():
+        s = ln.strip()
+        if depth:
+            if re.match(r"#\s*if", s):
+                depth += 1
+            elif re.match(r"#\s*endif", s):
+                depth -= 1
+            (inside if depth else outside).append(ln)
+        else:
+            outside.append(ln)
+            if re.match(r"#\s*if\s+D2PC_EXPERIMENTS\b", s):
+                depth = 1
+    assert depth == 0
+    return inside, outside
+
+
+def test_product_sources_define_nothing_of_the_laboratory():
+    """The product's sources (the Makefile's SRCS / HDRS) hold hooks to the laboratory, not its code: nothing between
+    `#if D2PC_EXPERIMENTS` and `#endif` defines a kernel, a device function, a template or a struct (the host-side
+    exceptions: the context's fields, the tuning keys and algorithm 4's state handling), and no product file includes a
+    laboratory file outside such a guard."""
+    files = [f for f in _make_list("SRCS") + _make_list("HDRS") if not f.startswith("../")]
+    assert len(files) > 30 and "d2pc_onepass.hip" in files and "d2pc_onepass_run.hpp" in files
+    # (every header beside the product's sources is in a list, so an #include of the laboratory cannot hide one level down)
+    assert sorted(f for f in _csrc_files(".hpp") if "/" not in f) == sorted(
+        f for f in files + _make_list("SECTORS_HDRS") if f.endswith(".hpp") and not f.startswith("../"))
+    guards = 0
+    for f in files:
+        text = open(os.path.join(CSRC, f)).read()
+        inside, outside = _split_guarded(text)
+        guards += bool(inside)
+        if f not in GUARD_EXEMPT:
+            for ln in inside:
+                code = ln.split("//")[0]
+                assert not re.search(r"\b(__global__|__device__|template|struct)\b", code), (f, ln)
+        assert not [ln for ln in outside if re.match(r"\s*#\s*include\b.*\blab/", ln)], f
+    assert guards >= 6      # the hooks exist: parity, onepass, compact, median_bs, launch.hpp, ...
+    assert not os.path.exists(os.path.join(CSRC, "d2pc_chunk.hip"))
+    for f in ("d2pc_onepass.hip", "d2pc_parity.hip", "d2pc_median_bs.hip", "d2pc_median_bs_tile.hpp"):
+        text = open(os.path.join(CSRC, f)).read()
+        for name in ("k_compact_onepass_lw", "TileFetchAll", "tile_scatter_lean", "k_reproject_pack(", "launch_walking",
+                     "k_median_bs2_u8", "median_bs2_tile("):
+            assert name not in re.sub(r"//.*", "", text), (f, name)
+
+
+def test_documents_name_existing_sources():
+    """Every d2pc_*.hip / d2pc_*.hpp the living documents name is a file under csrc/ (docs/HISTORY.md and profiles/ are
+    records of their time and exempt)."""
+    have = {os.path.basename(f) for f in _csrc_files(".hip", ".hpp")}
+    for doc in ("README.md", "INTEGRATION.md", "DESIGN.md", "tests/README.md", "tools/README.md"):
+        names = set(re.findall(r"\bd2pc_\w+\.(?:hip|hpp)\b", open(os.path.join(ROOT, doc)).read()))
+        assert names <= have, (doc, sorted(names - have))
 
 
 def test_stable_header_holds_no_tool_surface():

@@ -56,7 +56,7 @@ def test_bit_sliced_median_matches_oracle(k, w, h):
 @pytest.mark.parametrize("k", [3, 5, 7, 9, 11])
 def test_lane_pair_select_experiment_matches_oracle(k):
     """EXPERIMENT BUILD (median_algo 3, round 4's verdict item 3c): the bit-sliced select with the candidate window split
-    over a lane pair (select2 in d2pc_median_bs_tile.hpp: 66 instead of 121 candidate words per lane at 11 x 11, four waves
+    over a lane pair (select2 in lab/d2pc_median_bs2_tile.hpp: 66 instead of 121 candidate words per lane at 11 x 11, four waves
     per SIMD).  Same bytes as the oracle on tiles cut by every edge, ties, images smaller than the window."""
     rng = np.random.default_rng(3000 + k)
     for (w, h) in ((752, 480), (97, 131), (256, 32), (257, 33), (300, 70), (5, 3), (1, 1), (1, 40), (40, 1), (1037, 45)):

@@ -266,10 +266,12 @@ int d2pc_destroy(d2pc_ctx *ctx) {
   }
   for (hipEvent_t e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
+#if D2PC_EXPERIMENTS  // (the chunked overlap of lab/d2pc_capi_mono_overlap.hip)
   for (hipEvent_t e : ctx->cb_events) (void)hipEventDestroy(e);
   if (ctx->cb_stream_m) (void)hipStreamDestroy(ctx->cb_stream_m);
   if (ctx->cb_stream_r) (void)hipStreamDestroy(ctx->cb_stream_r);
   if (ctx->cb_overlap_done) (void)hipEventDestroy(ctx->cb_overlap_done);
+#endif
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return D2PC_OK;

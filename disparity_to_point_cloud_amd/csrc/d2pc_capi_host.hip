@@ -53,15 +53,15 @@ static int process_host_frame(d2pc_ctx *ctx, const void *disp, int dtype, float 
     return fail(ctx, D2PC_ERR_BAD_DTYPE, "dtype %d is not F32/U8/U16/MONO16", dtype);
   const int kdtype = bridge16 ? D2PC_DTYPE_U8 : dtype;  // what the kernels see
   const bool median = median_ksize > 1;
-  if (median && (kdtype != D2PC_DTYPE_U8 || !median_ksize_supported(median_ksize)))
-    return fail(ctx, D2PC_ERR_INVALID_ARG, "median needs 8-bit input and an odd ksize in 3..11 (got %d)", median_ksize);
+  int st;
+  if (median && (st = check_median(ctx, kdtype == D2PC_DTYPE_U8, median_ksize)) != D2PC_OK) return st;
   const size_t es = elem_size(dtype), kes = elem_size(kdtype);
   // device copies of the frame are packed to a 256-byte pitch
   const size_t pitch = (size_t(width > 0 ? width : 0) * es + 255) & ~size_t(255);
   const size_t kpitch = (size_t(width > 0 ? width : 0) * kes + 255) & ~size_t(255);
   const int pxt = compact ? ctx->pxt_compact : parity_pxt(ctx, width, height, 1);
   Geom g;
-  int st = make_geom(ctx, dtype, scale, width, height, row_stride, 0, 1, 0, pxt, &g);  // validates the caller's stride
+  st = make_geom(ctx, dtype, scale, width, height, row_stride, 0, 1, 0, pxt, &g);  // validates the caller's stride
   if (st != D2PC_OK) return st;
   if (g.roi_n == 0) return D2PC_OK;  // cpp:70,72: empty loops => empty cloud
   if (!out_points) return fail(ctx, D2PC_ERR_INVALID_ARG, "out_points is null");
@@ -103,32 +103,14 @@ static int process_host_frame(d2pc_ctx *ctx, const void *disp, int dtype, float 
     D2PC_HIP(ctx, hipMemcpy2DAsync(ctx->d_in, pitch, disp, row_stride, size_t(width) * es, size_t(height),
                                    hipMemcpyHostToDevice, s));
   D2PC_HIP(ctx, mark(1));
-  const void *kernel_in = direct_in ? direct_in : ctx->d_in;
-  size_t kernel_in_pitch = direct_in ? row_stride : pitch;
-  MedianArgs m;
-  m.algo = ctx->median_algo;
-  m.width = uint32_t(width);
-  m.height = uint32_t(height);
-  if (bridge16) {
-    m.src_row_stride = uint32_t(kernel_in_pitch);
-    m.dst_row_stride = uint32_t(kpitch);
-    D2PC_HIP(ctx, launch_mono16_to_mono8(kernel_in, ctx->d_cvt, m, s));
-    kernel_in = ctx->d_cvt;
-    kernel_in_pitch = kpitch;
-  }
-  if (median) {
-    m.src_row_stride = uint32_t(kernel_in_pitch);
-    m.dst_row_stride = uint32_t(kpitch);
-    median_roi_only(m, g, height);
-    D2PC_HIP(ctx, launch_median(kernel_in, ctx->d_med, m, median_ksize, s));
-    kernel_in = ctx->d_med;
-    kernel_in_pitch = kpitch;
-  }
-  if (kernel_in == direct_in) g = g_caller;  // the reprojection itself reads the caller's rows
+  // (rescale and median write copies packed to the same 256-byte pitch as the staged frame)
+  Frames k{direct_in ? direct_in : ctx->d_in, direct_in ? row_stride : pitch, 0};
+  if ((st = prepare_mono(ctx, &k, width, height, 1, bridge16, median_ksize, ctx->d_cvt, ctx->d_med, kpitch, 0, g, s)) != D2PC_OK) return st;
+  if (k.p == direct_in) g = g_caller;  // the reprojection itself reads the caller's rows
   D2PC_HIP(ctx, mark(2));
   void *kout = direct_out ? direct_out : ctx->d_out;
   uint32_t *kidx = !out_index ? nullptr : static_cast<uint32_t *>(direct_out ? direct_idx : ctx->d_idx);
-  st = enqueue(ctx, g, kernel_in, kdtype, kout, kidx, ctx->d_counts, s);
+  st = enqueue(ctx, g, k.p, kdtype, kout, kidx, ctx->d_counts, s);
   if (st != D2PC_OK) return st;
   D2PC_HIP(ctx, mark(3));
   size_t n = g.roi_n;
@@ -140,7 +122,7 @@ static int process_host_frame(d2pc_ctx *ctx, const void *disp, int dtype, float 
       // this entry point is synchronous, so run the frame again with the two-pass form, which cannot wait.
       // Counted: d2pc_compact_stats reports these reruns (twopass_fallbacks) and the launch that timed out.
       ++ctx->n_twopass_fallbacks;
-      st = enqueue(ctx, g, kernel_in, kdtype, kout, kidx, ctx->d_counts, s, nullptr, 1);
+      st = enqueue(ctx, g, k.p, kdtype, kout, kidx, ctx->d_counts, s, nullptr, 1);
       if (st != D2PC_OK) return st;
       D2PC_HIP(ctx, hipMemcpyAsync(ctx->h_counts, ctx->d_counts, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       D2PC_HIP(ctx, hipStreamSynchronize(s));
@@ -229,13 +211,13 @@ int d2pc_pipeline_acquire(d2pc_ctx *ctx, const d2pc_frame_desc *desc, void **hos
   if (!ctx->have_q) return fail(ctx, D2PC_ERR_NOT_CALIBRATED, "Q matrix not set");
   const bool median = desc->median_ksize > 1;
   const bool bridge16 = desc->dtype == D2PC_DTYPE_MONO16;  // cpp:50's rescale to 8 bits runs on the device
-  if (median && ((desc->dtype != D2PC_DTYPE_U8 && !bridge16) || !median_ksize_supported(desc->median_ksize)))
-    return fail(ctx, D2PC_ERR_INVALID_ARG, "median needs 8-bit (or MONO16) input and an odd ksize in 3..11");
+  int st;
+  if (median && (st = check_median(ctx, desc->dtype == D2PC_DTYPE_U8 || bridge16, desc->median_ksize)) != D2PC_OK) return st;
   DeviceGuard guard(ctx->device);
   Geom g;  // validates dtype / size / stride of the caller's layout
-  int st = make_geom(ctx, bridge16 ? int(D2PC_DTYPE_U16) : desc->dtype, desc->scale, desc->width, desc->height,
-                     desc->row_stride_bytes, 0, 1, 0,
-                     ctx->cfg.mode == D2PC_MODE_COMPACT ? ctx->pxt_compact : parity_pxt(ctx, desc->width, desc->height, 1), &g);
+  st = make_geom(ctx, bridge16 ? int(D2PC_DTYPE_U16) : desc->dtype, desc->scale, desc->width, desc->height,
+                 desc->row_stride_bytes, 0, 1, 0,
+                 ctx->cfg.mode == D2PC_MODE_COMPACT ? ctx->pxt_compact : parity_pxt(ctx, desc->width, desc->height, 1), &g);
   if (st != D2PC_OK) return st;
   int found = -1;
   for (int i = 0; i < ctx->pipe_depth; ++i)
@@ -301,23 +283,9 @@ int d2pc_pipeline_submit(d2pc_ctx *ctx, int slot) {
     }
   } drain{sl};
   D2PC_HIP(ctx, hipMemcpyAsync(sl.d_in, sl.h_in, in_bytes, hipMemcpyHostToDevice, s));
-  const void *kin = sl.d_in;
-  MedianArgs m;
-  m.algo = ctx->median_algo;
-  m.width = uint32_t(d.width);
-  m.height = uint32_t(d.height);
-  if (bridge16) {
-    m.src_row_stride = uint32_t(d.row_stride_bytes);
-    m.dst_row_stride = uint32_t(kstride);
-    D2PC_HIP(ctx, launch_mono16_to_mono8(sl.d_in, sl.d_cvt, m, s));
-    kin = sl.d_cvt;
-  }
-  if (d.median_ksize > 1) {
-    m.src_row_stride = m.dst_row_stride = uint32_t(kstride);
-    median_roi_only(m, g, d.height);
-    D2PC_HIP(ctx, launch_median(kin, sl.d_med, m, d.median_ksize, s));
-    kin = sl.d_med;
-  }
+  // (8-bit frames keep the caller's row stride through the median; MONO16's 8-bit copies are packed to kstride)
+  Frames k{sl.d_in, d.row_stride_bytes, 0};
+  if ((st = prepare_mono(ctx, &k, d.width, d.height, 1, bridge16, d.median_ksize, sl.d_cvt, sl.d_med, kstride, 0, g, s)) != D2PC_OK) return st;
   sl.h_count[0] = 0;
   if (g.roi_n) {
     // direct mode: the kernels store points (and indices) straight into the
@@ -326,7 +294,7 @@ int d2pc_pipeline_submit(d2pc_ctx *ctx, int slot) {
     uint32_t *kidx = !d.want_index ? nullptr
                      : ctx->pipe_direct ? reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(sl.h_out) + sl.idx_off)
                                         : static_cast<uint32_t *>(sl.d_idx);
-    st = enqueue(ctx, g, kin, kdtype, kout, kidx, sl.d_count, s, &sl.st);
+    st = enqueue(ctx, g, k.p, kdtype, kout, kidx, sl.d_count, s, &sl.st);
     if (st != D2PC_OK) return st;
     D2PC_HIP(ctx, hipMemcpyAsync(sl.h_count, sl.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (!ctx->pipe_direct) {

@@ -228,6 +228,41 @@ int enqueue(d2pc_ctx *ctx, const Geom &g, const void *d_disp, int dtype, void *d
   return D2PC_OK;
 }
 
+// The tile-fused COMPACT callback body (median + points per tile, row counts handed over between the tiles of a band).
+// Residency: sub-batches of at most nfc frames, launched back to back on the same stream (d2pc_route.hpp); `a` holds the
+// whole call (geometry, outputs, Q), `m` the filter with the ROI as its output rectangle, `src` the 8-bit frames.
+int enqueue_callback_compact(d2pc_ctx *ctx, const LaunchArgs &a, const MedianArgs &m, const void *src, int ksize) {
+  const Geom &g = a.geom;
+  const uint32_t tiles_x = cb_tiles_x(g.roi_w), tiles_y = cb_tiles_y(g.roi_n / g.roi_w);  // (ROI rows)
+  const CallbackCompactPlan cc =
+      plan_callback_compact(ctx->cu_count, ctx->cb_pipe_blocks_per_cu, ctx->cb_fused_compact, tiles_x, tiles_y, g.n_frames);
+  for (uint32_t s0 = 0; s0 < g.n_frames; s0 += cc.nfc) {
+    const uint32_t ns = g.n_frames - s0 < cc.nfc ? g.n_frames - s0 : cc.nfc;
+    LaunchArgs as = a;
+    as.keep_timeout = s0 > 0;  // one flag for the whole call: a later sub-batch's state clear must not wipe an earlier one's give-up
+    as.out_points = static_cast<uint8_t *>(a.out_points) + size_t(s0) * g.out_frame_stride * 16;
+    as.out_index = a.out_index ? a.out_index + size_t(s0) * g.out_frame_stride : nullptr;
+    as.counts = a.counts + s0;
+    as.geom.n_frames = ns;
+    as.geom.total_tiles = g.tiles_per_frame * ns;
+    as.state_bytes = callback_compact_state_bytes(tiles_x, tiles_y, ns, &as.geom.frame_state_stride);
+    as.stats = ctx->d_stats;
+    MedianArgs ms = m;
+    ms.n_frames = ns;
+    StateBuf *sb = nullptr;
+    int st = acquire_buf(ctx, ctx->states, a.stream, as.state_bytes, 0, nullptr, &sb);
+    if (st != D2PC_OK) return st;
+    bind_state(*sb, as, false);
+    sb->algo = 2;  // its header carries the hand-off's timeout flag, like the single pass's
+    const CallbackCompactPlan::Sub sub = cc.sub(ns);
+    as.compact_algo = sub.pipelined ? 2 : 1;
+    if (sub.pipelined) as.grid = sub.grid;  // (the one-tile-per-block form takes its grid from the launch's own tiles)
+    D2PC_HIP(ctx, launch_callback_bs_compact(as, ms, static_cast<const uint8_t *>(src) + size_t(s0) * g.in_frame_stride, ksize));
+    if (!sb->captured) sb->dirty = true;
+  }
+  return D2PC_OK;
+}
+
 }  // namespace host
 }  // namespace d2pc
 

@@ -3,9 +3,10 @@
 //   d2pc_capi_context.hip  status strings, calibration (Q, blob, closed forms), create / destroy, fill_q / classify_q
 //   d2pc_capi_state.hip    the pool of per-stream state buffers (lazy events, captures, self-cleaning halves, the resident
 //                          launches' epochs), d2pc_reserve*, d2pc_check_async_error, d2pc_compact_stats
-//   d2pc_capi_route.hip    launch geometry and one device-resident call carried out to its plan (enqueue), d2pc_process_device
+//   d2pc_capi_route.hip    launch geometry, one device-resident call carried out to its plan (enqueue, enqueue_callback_compact), d2pc_process_device
 //   d2pc_capi_host.hip     the synchronous host entry points (d2pc_process*) and the pipelined host path (d2pc_pipeline_*)
-//   d2pc_capi_mono.hip     cv_bridge rescale, median, the device-resident callback body (d2pc_process_mono_device)
+//   d2pc_capi_mono.hip     cv_bridge rescale, median: the ONE chain in front of the reprojection (prepare_mono, with its request
+//                          check and its MedianArgs maker) and the device-resident callback body (d2pc_process_mono_device)
 //   d2pc_capi_fusion.hip   depth-map fusion inner loop, rotate, crop
 //   d2pc_capi_node.hip     the depth_map_fusion node as a session (d2pc_fusion_node_*)
 //   d2pc_capi_rig.hip      a camera rig as a session (d2pc_rig_*: n cameras, n Qs in a device table, one merged cloud; d2pc_rig.hpp)
@@ -23,7 +24,8 @@
 //     d2pc_texture_device (the texture; d2pc_capi_rig.hip) Bound32::Pitch, FrameRule::LastRow; 16- / 32-bit samples aligned
 // The kernels behind d2pc_launch.hpp are one file per mode or filter beside these; the closed experiments' kernels are
 // lab/*.hip, which only the builds with -DD2PC_EXPERIMENTS=1 compile (the Makefile's LAB_SRCS) and which the product's
-// sources reach through the *_lab hooks of d2pc_launch.hpp alone (tests/test_abi_cpu.py holds that rule).
+// sources reach through the *_lab hooks of d2pc_launch.hpp alone (tests/test_abi_cpu.py holds that rule); one of them is host
+// code, lab/d2pc_capi_mono_overlap.hip: the callback body in chunks on two internal streams (process_mono_overlap_lab below).
 // Every exported symbol is unchanged (tests/test_abi_cpu.py::test_library_exports_every_declared_symbol), and nothing
 // else is exported: d2pc.map keeps d2pc::host::*, d2pc::launch_* and the kernel handles inside the library, since the
 // flavours define those names over different layouts of d2pc_ctx (::test_library_exports_nothing_undeclared).
@@ -178,7 +180,7 @@ struct d2pc_ctx {
   int membench_blocks_per_cu = 8;  // 0: one-shot blocks (one per membench_unroll x 4 KiB)
   int membench_unroll = 4;         // 16-byte accesses per thread and step: 1, 2 or 4
   int membench_nt = 0;             // non-temporal stores
-  // d2pc_process_mono_device: two internal streams + scratch for the filtered frames
+  // d2pc_process_mono_device
   int cb_fused_compact = 2;      // ... and the COMPACT form of that kernel: 2 = persistent blocks, software-pipelined over their
                                  // tiles (k_callback_bs_compact_pipe; the default: 16 x 4K with 30 % holes + indices 711 us
                                  // against 758 us for form 1 and 963 us as two launches, profiles/r03_callback_compact.txt);
@@ -187,12 +189,16 @@ struct d2pc_ctx {
   int cb_fused = 1;              // d2pc_process_mono_device, PARITY: median + points in one kernel, tile by tile (k_callback_bs:
                                  // bit-sliced median, the tile's points from LDS) when the launch is large enough for the
                                  // bit-sliced filter; 0 = always the filter launch followed by the reprojection launch
-  int cb_chunks = 1;             // pipeline chunks per call (<= 1: everything in order on the caller's stream;
-                                 // overlapping did not pay reliably: profiles/r02_callback_overlap.txt)
+#if D2PC_EXPERIMENTS
+  int cb_chunks = 1;             // lab/d2pc_capi_mono_overlap.hip: pipeline chunks per call (<= 1: everything in order on the caller's
+                                 // stream; overlapping did not pay reliably: profiles/r02_callback_overlap.txt)
   hipStream_t cb_stream_m = nullptr, cb_stream_r = nullptr;
   std::vector<hipEvent_t> cb_events;
   hipEvent_t cb_overlap_done = nullptr;  // the chunked-overlap form shares the two streams above: calls are serialised
   bool cb_overlap_pending = false;
+#else
+  static constexpr int cb_chunks = 1;  // (the product: the whole batch in order on the caller's stream)
+#endif
   // pipelined host path
   PipeSlot slots[8];
   int pipe_depth = 0;
@@ -250,6 +256,8 @@ void retile(Geom *g, int pxt);
 double w_safe_for(const d2pc_ctx *ctx, const Geom &g);
 int enqueue(d2pc_ctx *ctx, const Geom &g, const void *d_disp, int dtype, void *d_out, uint32_t *d_idx, uint32_t *d_counts,
             hipStream_t stream, StateBuf *fixed_state = nullptr, int force_algo = 0, uint32_t call_epoch_first = 0);
+// the tile-fused COMPACT callback body: a.geom's frames in sub-batches that stay resident, back to back on a.stream
+int enqueue_callback_compact(d2pc_ctx *ctx, const LaunchArgs &a, const MedianArgs &m, const void *src, int ksize);
 
 // ---- d2pc_capi_state.hip ---------------------------------------------------------------------------------------------
 bool capture_info(hipStream_t s, unsigned long long *id);
@@ -270,9 +278,28 @@ void bind_state(StateBuf &sb, LaunchArgs &a, bool self_clean);
 int fill_q(d2pc_ctx *ctx, LaunchArgs &a, int width);
 void classify_q(d2pc_ctx *ctx);
 
-// ---- d2pc_capi_host.hip / d2pc_capi_mono.hip ---------------------------------------------------------------------------
+// ---- d2pc_capi_host.hip ----------------------------------------------------------------------------------------------
 void *pinned_device_view(const void *p, size_t bytes);
+
+// ---- d2pc_capi_mono.hip: what happens to a mono image in front of the reprojection (reference cpp:50-57) -------------------
+struct Frames { const void *p; size_t pitch, frame; };  // device frames as a kernel sees them: bytes between rows, between frames
+int check_median(d2pc_ctx *ctx, bool eight_bit, int ksize);  // "median needs 8-bit input and a supported ksize": D2PC_ERR_INVALID_ARG
+MedianArgs median_args(const d2pc_ctx *ctx, int width, int height, int n_frames, size_t src_pitch, size_t src_frame,
+                       size_t dst_pitch, size_t dst_frame);
 void median_roi_only(MedianArgs &m, const Geom &g, int height);
+// Enqueues on `s` the mono16 -> mono8 rescale of *in into d_cvt (if `rescale`) and the median of `roi`'s ROI into d_med (if
+// ksize > 1), both at kpitch / kframe; *in becomes what the reprojection reads.  It invents no pitch.  The callers': synchronous
+// host path, every device copy packed to 256 bytes; pipelined path, the caller's row stride for 8-bit frames and 256 for MONO16's
+// 8-bit copies; d2pc_process_mono_device, the caller's layout for the input and 256 for its scratch.
+int prepare_mono(d2pc_ctx *ctx, Frames *in, int width, int height, int n_frames, bool rescale, int ksize, void *d_cvt,
+                 void *d_med, size_t kpitch, size_t kframe, const Geom &roi, hipStream_t s);
+#if D2PC_EXPERIMENTS
+// lab/d2pc_capi_mono_overlap.hip: the two-launch form in chunks of `chunk` frames, prepare_mono on one internal stream
+// beside enqueue on another (CallbackPlan::overlap); arguments as prepare_mono's and d2pc_process_mono_device's
+int process_mono_overlap_lab(d2pc_ctx *ctx, Frames in, int width, int height, int n_frames, int chunk, bool rescale, int ksize,
+                             void *d_cvt, void *d_med, size_t kpitch, size_t kframe, const Geom &roi, float scale, int pxt,
+                             void *d_out, uint32_t *d_idx, size_t out_frame_stride, uint32_t *d_counts, hipStream_t user);
+#endif
 
 }  // namespace host
 }  // namespace d2pc

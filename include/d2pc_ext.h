@@ -105,7 +105,7 @@ int d2pc_last_stage_times(d2pc_ctx *ctx, d2pc_stage_times *times);
  * 3 for 4K-class frames, 4 below), "resident_pxt" (shape of the one-launch
  * resident forms), "no_vec_rows", "fuse_rows" (rows per wave of d2pc_fuse_device: 0 = choose, else even 2..1024),
  * "stage_timing" (0/1, see d2pc_last_stage_times), "spin_timeout_ms" (1..40000: time budget of the in-launch hand-off
- * waits), "callback_chunks" (0..64 pipeline chunks of d2pc_process_mono_device; <= 1 = no overlap),
+ * waits), "callback_chunks" (0 or 1: d2pc_process_mono_device serves its batch in order on the caller's stream),
  * "callback_fused" (0/1, see d2pc_process_mono_device; default 1), "callback_fused_compact" (COMPACT mode: 0 = two
  * launches, 1 = one tile per block, 2 = persistent blocks that scatter one tile while filtering the next; default 2),
  * "callback_pipe_blocks_per_cu" (1..8, default 3), "membench_blocks_per_cu" (d2pc_membench_*: persistent blocks per
@@ -128,7 +128,9 @@ int d2pc_last_stage_times(d2pc_ctx *ctx, d2pc_stage_times *times);
  * resident); "pxt_parity" 4 / 8 / 16 (the tile-walking PARITY kernel of rounds 1-2) and "parity_small"; "pxt_compact" 4 / 16;
  * "onepass_form" 1 (rounds 2-4's single pass) and 3-7 (round 5's other forms: 8 worker waves, loader wave, 4 runs per
  * wave, deferred landing, both -- profiles/r05_ab_onepass_forms_*.txt, r05_ab_forms567.txt); "median_algo" 3 (the select
- * split over a lane pair); test hook "general_q_form" = 1 (round 2's fused evaluation of a general Q). */
+ * split over a lane pair); "callback_chunks" 2..64 (round 2's chunked overlap: d2pc_process_mono_device cuts its batch into
+ * that many chunks, the filter of one on an internal stream beside the reprojection of another on a second one;
+ * profiles/r02_callback_overlap.txt); test hook "general_q_form" = 1 (round 2's fused evaluation of a general Q). */
 int d2pc_set_tuning(d2pc_ctx *ctx, const char *key, int value);
 
 

@@ -138,6 +138,27 @@ def test_product_sources_define_nothing_of_the_laboratory():
             assert name not in re.sub(r"//.*", "", text), (f, name)
 
 
+def test_the_mono_chain_is_written_once_and_the_product_overlaps_nothing():
+    """Rescale -> median -> points: the two filter launches stand in d2pc_capi_mono.hip only (prepare_mono and the two
+    device entry points), and the product's callback body owns no stream and no event -- the chunked overlap is the
+    laboratory's (lab/d2pc_capi_mono_overlap.hip)."""
+    product = {}
+    for f in ("d2pc_capi_mono.hip", "d2pc_capi_host.hip"):
+        _, outside = _split_guarded(open(os.path.join(CSRC, f)).read())
+        product[f] = "\n".join(ln.split("//")[0] for ln in outside)
+        for word in ("cb_stream_", "cb_events"):
+            assert word not in product[f], (f, word)
+        # (the one stream either file creates is a pipeline slot's, in d2pc_pipeline_configure)
+        creates = [ln for ln in product[f].splitlines() if "hipStreamCreate" in ln]
+        assert len(creates) == (f == "d2pc_capi_host.hip") and all("&sl.stream" in ln for ln in creates), (f, creates)
+    for call in ("launch_median(", "launch_mono16_to_mono8("):
+        assert call in product["d2pc_capi_mono.hip"] and call not in product["d2pc_capi_host.hip"], call
+        for f in _make_list("SRCS"):
+            if f.startswith("d2pc_capi_") and f != "d2pc_capi_mono.hip":
+                assert call not in re.sub(r"//.*", "", open(os.path.join(CSRC, f)).read()), (f, call)
+    assert "lab/d2pc_capi_mono_overlap.hip" in _make_list("LAB_SRCS")
+
+
 def test_documents_name_existing_sources():
     """Every d2pc_*.hip / d2pc_*.hpp the living documents name is a file under csrc/ (docs/HISTORY.md and profiles/ are
     records of their time and exempt)."""

@@ -337,8 +337,9 @@ def test_process_mono_device_compact_warm_up_then_capture_on_the_same_stream(fus
 @pytest.mark.parametrize("chunks", [2, 0, 4])
 def test_process_mono_device_is_the_callback_body_for_a_batch(mode, dtype, chunks):
     """d2pc_process_mono_device: (rescale ->) median 11 over the ROI -> x 1/8 -> reproject for a device-resident
-    batch, cut into `callback_chunks` chunks pipelined over two internal streams (<= 1: everything in order on
-    the caller's stream).  The split must never show in the result."""
+    batch.  The product serves it in order on the caller's stream (`callback_chunks` 0 / 1, the only values it takes);
+    the EXPERIMENT BUILD cuts it into `callback_chunks` chunks pipelined over two internal streams
+    (lab/d2pc_capi_mono_overlap.hip).  The split must never show in the result."""
     from disparity_to_point_cloud_amd.torch_api import DeviceBatch
     q = d2pc.make_q()
     rng = np.random.default_rng(mode * 10 + chunks)
@@ -351,7 +352,12 @@ def test_process_mono_device_is_the_callback_body_for_a_batch(mode, dtype, chunk
         imgs = rng.integers(0, 65536, size=(n, h, w)).astype(np.uint16)
         src = torch.from_numpy(imgs.view(np.int16)).cuda()
         m8, dt, rs = np.stack([oracle.mono16_to_mono8(i) for i in imgs]), d2pc.DTYPE_MONO16, 2 * w
-    with d2pc.Context(q=q, mode=mode) as ctx:
+    with d2pc.Context(q=q, mode=mode, variant="exp" if chunks > 1 else None) as ctx:
+        if chunks <= 1:   # the product library: nothing to cut the batch with
+            with pytest.raises(d2pc.D2pcError) as e:
+                ctx.set_tuning("callback_chunks", 2)
+            assert e.value.status == 1   # D2PC_ERR_INVALID_ARG
+            ctx.set_tuning("callback_chunks", 1)
         ctx.set_tuning("callback_chunks", chunks)           # 7 frames: chunks of 4+3 / 2+2+2+1
         b = DeviceBatch(ctx, n, h, w, dtype=torch.uint8, want_index=True)
         side = torch.cuda.Stream()
@@ -374,6 +380,62 @@ def test_process_mono_device_is_the_callback_body_for_a_batch(mode, dtype, chunk
             want, wi = oracle.reproject_compact(filt, q, border=40, scale=0.125)
             assert np.array_equal(idx, wi)
         assert_points_close(pts, want, max_ulp=1, rel=1e-5, what=f"frame {f}")
+
+
+@pytest.mark.parametrize("mode", [d2pc.MODE_PARITY, d2pc.MODE_COMPACT])
+@pytest.mark.parametrize("dtype", ["u8", "mono16"])
+@pytest.mark.parametrize("k", [3, 11])
+def test_the_three_doors_of_the_callback_body_give_the_same_cloud(mode, dtype, k):
+    """One frame through the three entry points that run (rescale ->) median(ROI) -> reproject: d2pc_process_mono8 / 16
+    (pageable numpy), the pipelined host path (staged and direct_host_write) and d2pc_process_mono_device with one frame.
+    Each keeps its own pitches -- the synchronous path packs to 256 bytes, the pipeline keeps the caller's stride for
+    8-bit frames, the device path reads the caller's layout and packs its scratch -- so the shape is one at which a
+    mix-up shows: 333 samples a row (no multiple of 256 bytes), caller rows padded by 13 samples that hold the largest
+    value (read as pixels they would change the median), border 5 < the window's reach.  Every door equals the oracle
+    (indices exact, points within 1 ulp) and the doors equal each other bit for bit."""
+    from textured_expect import roi_pixels
+    q = d2pc.make_q()
+    w, h, border, pad = 333, 70, 5, 13
+    u8 = dtype == "u8"
+    np_dt, top = (np.uint8, 255) if u8 else (np.uint16, 65535)
+    rng = np.random.default_rng(4 * k + 2 * mode + u8)
+    wide = np.full((h, w + pad), top, dtype=np_dt)
+    wide[:, :w] = rng.integers(0, top + 1, size=(h, w))
+    wide[:, :w][rng.random((h, w)) < 0.3] = 0
+    wide[20:45, 100:200] = 0                      # holes that survive the filter: COMPACT drops points
+    img = wide[:, :w]                             # the caller's rows: w + 13 samples apart
+    m8 = np.ascontiguousarray(img) if u8 else oracle.mono16_to_mono8(np.ascontiguousarray(img))
+    filt = oracle.median_u8(m8, k)
+    if mode == d2pc.MODE_PARITY:
+        want_p, want_i = oracle.reproject(filt, q, border=border, scale=0.125), roi_pixels(h, w, border)
+    else:
+        want_p, want_i = oracle.reproject_compact(filt, q, border=border, scale=0.125)
+        assert 0 < len(want_i) < (w - 2 * border) * (h - 2 * border)
+    roi_n = (w - 2 * border) * (h - 2 * border)
+    doors = {}
+    with d2pc.Context(q=q, border=border, mode=mode) as ctx:
+        doors["synchronous"] = (ctx.process_mono8 if u8 else ctx.process_mono16)(img, k, 0.125, want_index=True)
+        for direct in (False, True):
+            ctx.pipeline_configure(depth=1, direct_host_write=direct)
+            ctx.pipeline_submit(np.ascontiguousarray(img), scale=0.125, median_ksize=k, want_index=True, mono16=not u8)
+            doors["pipeline, direct" if direct else "pipeline, staged"] = ctx.pipeline_collect()[:2]
+        src = torch.from_numpy(wide if u8 else wide.view(np.int16)).cuda()
+        pts = torch.zeros((roi_n, 4), dtype=torch.float32, device="cuda")
+        idx = torch.full((roi_n,), -1, dtype=torch.int32, device="cuda")
+        cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+        rs = wide.strides[0]
+        ctx.process_mono_device(src.data_ptr(), d2pc.DTYPE_U8 if u8 else d2pc.DTYPE_MONO16, w, h, rs, rs * h, 1, k, 0.125,
+                                pts.data_ptr(), idx.data_ptr(), roi_n, cnt.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        ctx.check_async_error()
+        n = roi_n if mode == d2pc.MODE_PARITY else int(cnt.item())
+        doors["device"] = (pts.cpu().numpy()[:n], idx.cpu().numpy().view(np.uint32)[:n])
+    for name, (p, i) in doors.items():
+        assert np.array_equal(i, want_i), name
+        assert_points_close(p, want_p, max_ulp=1, what=name)
+    first_p = doors["synchronous"][0]      # (the indices are equal already: each equals the oracle's)
+    for name, (p, _) in doors.items():
+        assert np.array_equal(p.view(np.uint32), first_p.view(np.uint32)), f"{name} differs from the synchronous door"
 
 
 def test_process_mono_device_rejects_bad_arguments_and_runs_in_order_under_capture():

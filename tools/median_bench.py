@@ -58,6 +58,8 @@ for (w, h, n) in ((752, 480, 64), (1920, 1080, 16), (3840, 2160, 16)):
                                                b.points.data_ptr(), None, b.stride, b.counts.data_ptr(), s))
         print(f"{w}x{h} x{n}: d2pc_process_mono_device callback_fused={fused}: {uf:8.1f} us = "
               f"{n*w*h/uf:9.1f} Mpix/s  ({us/uf:.3f}x the two launches in order)", flush=True)
+    ctx.close()
+    ctx = d2pc.Context(q=q, variant=None if len(sys.argv) > 1 else "exp")  # the chunked overlap lives in the experiment build
     ctx.set_tuning("callback_fused", 0)
     for chunks in (2, 4):
         ctx.set_tuning("callback_chunks", chunks)

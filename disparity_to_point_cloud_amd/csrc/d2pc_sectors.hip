@@ -15,6 +15,10 @@
 //                    -DD2PC_SECTORS_FORCE_ROUNDS=0 / =2 build the two arms (tools/sectors_bench.py --ab).
 //                    At the end the block stores its table to its own slab with plain vector stores: no global atomic,
 //                    nothing to clear, no protocol between blocks.
+//                    A template on the layer kind.  <HEIGHT> is the statements above and nothing else.  <ELEVATION> keeps
+//                    the elevation table (ce_i, se_i) in LDS behind the azimuth table, gates on the Euclidean d2 and on the
+//                    band's two boundaries, counts the interior boundaries below the point in a second loop of the azimuth
+//                    loop's shape (one broadcast LDS read per boundary serves the lane's four records) and keys on d2.
 // k_sectors_finish   min / sum over the slabs, coalesced across cells (8 cells x 32 slices of the slabs per block, a
 //                    tree through LDS over the slices), then the outputs the caller asked for.
 // Keys are integers and counts are sums of integers: the result is the same bytes whatever order lanes, waves and
@@ -97,15 +101,19 @@ __device__ __forceinline__ void merge(unsigned long long *keys, uint32_t *cnts, 
   }
 }
 
+template <int kKind>
 __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
 #pragma clang fp contract(off)
+  constexpr bool kElevation = kKind == D2PC_SECTORS_LAYERS_ELEVATION;
   extern __shared__ __align__(16) unsigned char lds[];
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(lds);
   uint32_t *cnts = reinterpret_cast<uint32_t *>(keys + a.n_cells);
   float2 *tab = reinterpret_cast<float2 *>(cnts + a.n_cells);   // (n_cells is even: 8-byte aligned)
+  [[maybe_unused]] const float2 *etab = tab + a.half;           // n_layers + 1 x (ce, se), behind the azimuth table
   const uint32_t tid = threadIdx.x;
   for (int i = int(tid); i < a.n_cells; i += kThreads) keys[i] = ~0ull, cnts[i] = 0u;
-  for (int j = int(tid); j < a.half; j += kThreads) tab[j] = a.table[j];
+  // (the session's device table holds the elevation table behind the azimuth table, as the LDS does)
+  for (int j = int(tid); j < a.half + (kElevation ? a.n_layers + 1 : 0); j += kThreads) tab[j] = a.table[j];
   __syncthreads();
 
   for (uint64_t share = blockIdx.x; share < a.shares; share += uint64_t(a.blocks)) {
@@ -135,7 +143,10 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
     }
     float f[kPerLane], l[kPerLane];
     uint32_t cell[kPerLane], r2_bits[kPerLane], sector[kPerLane];
+    [[maybe_unused]] float up[kPerLane], hz[kPerLane];   // elevation: u and the horizontal range h = sqrtf(r2)
     const float2 t0 = tab[0];
+    [[maybe_unused]] float2 lo, hi;   // elevation: the band's two boundaries
+    if constexpr (kElevation) lo = etab[0], hi = etab[a.n_layers];
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
       const uint4 p = rec[k];
@@ -143,11 +154,22 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
       const float ff = pick(p, a.axis[0], a.flip[0]), ll = pick(p, a.axis[1], a.flip[1]);
       const float u = pick(p, a.axis[2], a.flip[2]);
       const float r2 = ff * ff + ll * ll;
-      const bool in = have[k] && finite && r2 > 0.0f && r2 >= a.rmin2 && r2 <= a.rmax2 && u >= a.u_min && u < a.u_max;
+      bool in;
       uint32_t layer = 0;
-      if (a.n_layers > 1) {
-        const float slab = floorf((u - a.u_min) * a.inv_h);
-        layer = slab >= float(a.n_layers - 1) ? uint32_t(a.n_layers - 1) : uint32_t(int(slab));   // (in: slab >= 0)
+      float key = r2;
+      if constexpr (kElevation) {
+        // the band's two boundaries are gates; `!(t >= 0)` and `t >= 0` as written: a NaN t (0 * inf) takes no part
+        const float h = __builtin_sqrtf(r2);   // (the correctly rounded one: the file's flags)
+        key = r2 + u * u;
+        const float t_lo = lo.x * u - lo.y * h, t_hi = hi.x * u - hi.y * h;
+        in = have[k] && finite && r2 > 0.0f && key >= a.rmin2 && key <= a.rmax2 && t_lo >= 0.0f && !(t_hi >= 0.0f);
+        up[k] = u, hz[k] = h;
+      } else {
+        in = have[k] && finite && r2 > 0.0f && r2 >= a.rmin2 && r2 <= a.rmax2 && u >= a.u_min && u < a.u_max;
+        if (a.n_layers > 1) {
+          const float slab = floorf((u - a.u_min) * a.inv_h);
+          layer = slab >= float(a.n_layers - 1) ? uint32_t(a.n_layers - 1) : uint32_t(int(slab));   // (in: slab >= 0)
+        }
       }
       const float cross0 = t0.x * ll - t0.y * ff, dot0 = t0.x * ff + t0.y * ll;
       // the half turn as a sign-bit mask, without a branch: hipcc of ROCm 7 structurised `if (A || (B && C)) negate` so
@@ -156,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
       f[k] = __uint_as_float(__float_as_uint(ff) ^ turn), l[k] = __uint_as_float(__float_as_uint(ll) ^ turn);
       sector[k] = turn ? uint32_t(a.half) : 0u;
       cell[k] = in ? layer * uint32_t(a.n_sectors) : kNone;
-      r2_bits[k] = __float_as_uint(r2);
+      r2_bits[k] = __float_as_uint(key);
     }
     // the count of the boundaries behind the point: one LDS read of (c_j, s_j) serves the lane's four records, and
     // every lane reads the same address (a broadcast: no bank conflict)
@@ -164,6 +186,17 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
       const float2 t = tab[j];
 #pragma unroll
       for (int k = 0; k < kPerLane; ++k) sector[k] += (t.x * l[k] - t.y * f[k]) >= 0.0f ? 1u : 0u;
+    }
+    if constexpr (kElevation) {
+      // the layer: the interior boundaries at or below the point, counted like the sectors (a compare folded into an add)
+      uint32_t layer[kPerLane] = {};
+      for (int i = 1; i < a.n_layers; ++i) {
+        const float2 t = etab[i];
+#pragma unroll
+        for (int k = 0; k < kPerLane; ++k) layer[k] += (t.x * up[k] - t.y * hz[k]) >= 0.0f ? 1u : 0u;
+      }
+#pragma unroll
+      for (int k = 0; k < kPerLane; ++k) sector[k] += layer[k] * uint32_t(a.n_sectors);   // (cell[k] is 0 or kNone here)
     }
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
@@ -220,10 +253,17 @@ __global__ __launch_bounds__(kThreads) void k_sectors_finish(const Args a) {
 
 }  // namespace
 
-int prepare_sectors_kernels(size_t lds_bytes) {
-  // beyond 64 KB of dynamic LDS the runtime wants to be told (360 x 16 cells need 70,560 bytes)
-  if (lds_bytes <= 64u * 1024u) return int(hipSuccess);
-  return int(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sectors_reduce), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+// the instantiation a session of plan `p` launches
+const void *reduce_kernel(const Plan &p) {
+  return p.layer_kind == D2PC_SECTORS_LAYERS_ELEVATION ? reinterpret_cast<const void *>(&k_sectors_reduce<D2PC_SECTORS_LAYERS_ELEVATION>)
+                                                       : reinterpret_cast<const void *>(&k_sectors_reduce<D2PC_SECTORS_LAYERS_HEIGHT>);
+}
+
+int prepare_sectors_kernels(const Plan &p) {
+  // beyond 64 KB of dynamic LDS the runtime wants to be told (360 x 16 cells need 70,560 bytes, 90 x 64 elevation cells
+  // 70,000), for the instantiation that is launched
+  if (p.lds_bytes <= 64u * 1024u) return int(hipSuccess);
+  return int(hipFuncSetAttribute(reduce_kernel(p), hipFuncAttributeMaxDynamicSharedMemorySize, int(p.lds_bytes)));
 }
 
 int launch_sectors(const Launch &in) {
@@ -245,7 +285,10 @@ int launch_sectors(const Launch &in) {
   for (int i = 0; i < 3; ++i) a.axis[i] = p.axis[i], a.flip[i] = p.flip[i];
   a.min_count = p.min_count, a.no_obstacle_cm = p.no_obstacle_cm;
   hipStream_t s = static_cast<hipStream_t>(in.stream);
-  hipLaunchKernelGGL(k_sectors_reduce, dim3(unsigned(in.blocks)), dim3(kThreads), p.lds_bytes, s, a);
+  if (p.layer_kind == D2PC_SECTORS_LAYERS_ELEVATION)
+    hipLaunchKernelGGL(k_sectors_reduce<D2PC_SECTORS_LAYERS_ELEVATION>, dim3(unsigned(in.blocks)), dim3(kThreads), p.lds_bytes, s, a);
+  else
+    hipLaunchKernelGGL(k_sectors_reduce<D2PC_SECTORS_LAYERS_HEIGHT>, dim3(unsigned(in.blocks)), dim3(kThreads), p.lds_bytes, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return int(e);
   hipLaunchKernelGGL(k_sectors_finish, dim3(unsigned((p.n_cells + kFinishCells - 1) / kFinishCells)), dim3(kThreads), 0, s, a);

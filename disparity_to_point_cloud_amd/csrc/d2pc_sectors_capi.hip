@@ -1,5 +1,5 @@
 // d2pc_sectors_capi.hip -- include/d2pc_sectors.h: the session (the boundary table and the blocks' slabs in device
-// memory) and the one asynchronous call.  Everything that needs no device -- the refusals, rmin2 / rmax2 / inv_h, the
+// memory; an elevation session's second table behind it) and the one asynchronous call.  Everything that needs no device -- the refusals, rmin2 / rmax2 / inv_h, the
 // table's values -- is d2pc_sectors_plan.hpp's; this file adds the device.  libd2pc_sectors.so links the HIP runtime
 // only: nothing of d2pc_ctx is needed to read records from device memory.
 #include <hip/hip_runtime.h>
@@ -16,7 +16,7 @@ struct d2pc_sectors {
   d2pc_sectors_config cfg{};
   Plan plan{};
   int device = 0, blocks = 0;
-  float *d_table = nullptr;         // half x (c, s)
+  float *d_table = nullptr;         // half x (c, s), then plan.elev x (ce, se)
   uint64_t *d_slab_keys = nullptr;  // blocks x n_cells
   uint32_t *d_slab_counts = nullptr;
   char err[256] = "";
@@ -79,6 +79,17 @@ int d2pc_sectors_table(const d2pc_sectors_config *cfg, float *c, float *s, int c
   return p.half;
 }
 
+int d2pc_sectors_elevation_table(const d2pc_sectors_config *cfg, float *c, float *s, int capacity) {
+  if (!c || !s) return -D2PC_ERR_INVALID_ARG;
+  Plan p;
+  const int st = make_plan(cfg, &p);
+  if (st != D2PC_OK) return -st;
+  if (p.layer_kind != D2PC_SECTORS_LAYERS_ELEVATION) return -D2PC_ERR_INVALID_ARG;
+  if (capacity < p.elev) return -D2PC_ERR_CAPACITY;
+  fill_elevation_table(*cfg, c, s);
+  return p.elev;
+}
+
 void d2pc_sectors_desc_init(d2pc_sectors_desc *desc) {
   if (!desc) return;
   memset(desc, 0, sizeof *desc);
@@ -112,15 +123,17 @@ int d2pc_sectors_create(const d2pc_sectors_config *cfg, d2pc_sectors **out) {
   if (!s) return D2PC_ERR_OUT_OF_MEMORY;
   s->cfg = *cfg, s->plan = p, s->device = cfg->device_id;
   s->blocks = p.blocks_per_cu * cus;
-  std::vector<float> table(size_t(p.half) * 2), cs(size_t(p.half)), sn(size_t(p.half));
+  const size_t pairs = size_t(p.half) + size_t(p.elev);
+  std::vector<float> table(pairs * 2), cs(pairs), sn(pairs);
   fill_table(*cfg, cs.data(), sn.data());
-  for (int j = 0; j < p.half; ++j) table[2 * size_t(j)] = cs[size_t(j)], table[2 * size_t(j) + 1] = sn[size_t(j)];
+  if (p.elev) fill_elevation_table(*cfg, cs.data() + p.half, sn.data() + p.half);
+  for (size_t j = 0; j < pairs; ++j) table[2 * j] = cs[j], table[2 * j + 1] = sn[j];
   const size_t cells = size_t(s->blocks) * size_t(p.n_cells);
   hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->d_table), table.size() * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_slab_keys), cells * sizeof(uint64_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_slab_counts), cells * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemcpy(s->d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipError_t(prepare_sectors_kernels(p.lds_bytes));
+  if (e == hipSuccess) e = hipError_t(prepare_sectors_kernels(p));
   if (e != hipSuccess) {
     (void)d2pc_sectors_destroy(s);
     return e == hipErrorOutOfMemory ? D2PC_ERR_OUT_OF_MEMORY : D2PC_ERR_DEVICE;

@@ -1,7 +1,8 @@
 // d2pc_sectors_plan.hpp -- the host side of include/d2pc_sectors.h that needs no device: what a configuration and a
 // descriptor are refused for, the constants the specification forms on the host (rmin2, rmax2, inv_h, the boundary
-// table) and the sizes of a block's tables.  Host code only and no HIP: plain g++ compiles it, and the checks run
-// wherever the library loads (tests/test_sectors_cpu.py, through d2pc_sectors_geometry / _table / _desc_check).
+// tables) and the sizes of a block's tables.  Host code only and no HIP: plain g++ compiles it, and the checks run
+// wherever the library loads (tests/test_sectors_cpu.py, tests/test_sectors_elevation_cpu.py, through
+// d2pc_sectors_geometry / _table / _elevation_table / _desc_check).
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -19,10 +20,13 @@ constexpr int kPerLane = D2PC_SECTORS_SHARE_POINTS / kThreads;    // records a l
 constexpr int kMaxBlocksPerCu = 4;
 constexpr size_t kLdsPerCu = 160u * 1024u;                        // gfx950
 constexpr int kRefCus = 256;                                      // MI355X: what geometry's device_bytes assumes
+constexpr int kMaxCells = D2PC_SECTORS_MAX_SECTORS * D2PC_SECTORS_MAX_LAYERS;   // the largest table a block holds
+constexpr float kHalfPi = 1.5707964f;                             // the float nearest pi / 2: an elevation band's bound
 static_assert(kPerLane * kThreads == D2PC_SECTORS_SHARE_POINTS, "a share is a whole number of records per lane");
 
 struct Plan {                // what the kernels get of a configuration
   int n_sectors, n_layers, n_cells, half;
+  int layer_kind, elev;      // elev: entries of the elevation table, n_layers + 1; 0 for height layers
   float rmin2, rmax2, u_min, u_max, inv_h;
   int axis[3];               // 0, 1, 2: the coordinate picked for f, l, u
   uint32_t flip[3];          // 0x80000000 where the pick negates
@@ -54,10 +58,23 @@ inline int make_plan(const d2pc_sectors_config *c, Plan *p, char *msg = nullptr,
   if (c->u_min > c->u_max) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "u_min > u_max");
   if (c->min_count < 1) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "min_count of %d", c->min_count);
   if (c->no_obstacle_cm > 65535u) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "no_obstacle_cm of %u does not fit 16 bits", c->no_obstacle_cm);
-  if (c->n_layers < 1 || c->n_layers > D2PC_SECTORS_MAX_LAYERS)
-    D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "n_layers of %d: 1 .. %d", c->n_layers, D2PC_SECTORS_MAX_LAYERS);
+  // (after every other INVALID_ARG and before the first BAD_SIZE: no status of a height-mode configuration moves)
+  if (c->layer_kind != D2PC_SECTORS_LAYERS_HEIGHT && c->layer_kind != D2PC_SECTORS_LAYERS_ELEVATION)
+    D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "layer_kind of %d: 0 (height) or 1 (elevation)", c->layer_kind);
+  p->layer_kind = c->layer_kind, p->elev = 0;
   p->inv_h = 0.0f;
-  if (c->n_layers > 1) {
+  if (c->layer_kind == D2PC_SECTORS_LAYERS_ELEVATION) {
+    if (c->n_layers < 1 || c->n_layers > D2PC_SECTORS_MAX_ELEVATION_LAYERS)
+      D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "n_layers of %d: 1 .. %d elevation layers", c->n_layers, D2PC_SECTORS_MAX_ELEVATION_LAYERS);
+    if (c->n_sectors * c->n_layers > kMaxCells)
+      D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "%d x %d cells: %d at the most", c->n_sectors, c->n_layers, kMaxCells);
+    if (!(c->u_min >= -kHalfPi) || !(c->u_max <= kHalfPi))   // (infinities included)
+      D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the elevation band must lie within -+1.5707964 rad");
+    if (c->u_min == c->u_max) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the elevation band is empty");
+    p->elev = c->n_layers + 1;
+  } else if (c->n_layers < 1 || c->n_layers > D2PC_SECTORS_MAX_LAYERS) {
+    D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "n_layers of %d: 1 .. %d", c->n_layers, D2PC_SECTORS_MAX_LAYERS);
+  } else if (c->n_layers > 1) {
     if (!std::isfinite(c->u_min) || !std::isfinite(c->u_max) || !(c->u_min < c->u_max))
       D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "%d layers need a finite height band with u_min < u_max", c->n_layers);
     p->inv_h = float(double(c->n_layers) / (double(c->u_max) - double(c->u_min)));
@@ -72,8 +89,8 @@ inline int make_plan(const d2pc_sectors_config *c, Plan *p, char *msg = nullptr,
   }
   p->u_min = c->u_min, p->u_max = c->u_max;
   p->min_count = uint32_t(c->min_count), p->no_obstacle_cm = c->no_obstacle_cm;
-  // LDS of a block: 8-byte keys, 4-byte counts, then the table's (c, s) pairs
-  p->lds_bytes = size_t(p->n_cells) * 12u + size_t(p->half) * 8u;
+  // LDS of a block: 8-byte keys, 4-byte counts, then the table's (c, s) pairs, then the elevation table's
+  p->lds_bytes = size_t(p->n_cells) * 12u + size_t(p->half) * 8u + size_t(p->elev) * 8u;
   p->block_bytes = size_t(p->n_cells) * 12u;
   const size_t fit = kLdsPerCu / p->lds_bytes;
   p->blocks_per_cu = int(fit < size_t(kMaxBlocksPerCu) ? fit : size_t(kMaxBlocksPerCu));
@@ -86,8 +103,9 @@ inline void fill_geometry(const Plan &p, d2pc_sectors_geometry_t *g) {
   g->rmin2 = p.rmin2, g->rmax2 = p.rmax2, g->inv_h = p.inv_h;
   g->share_points = D2PC_SECTORS_SHARE_POINTS;
   g->blocks_per_cu = p.blocks_per_cu;
+  g->elevation_entries = p.elev;
   g->lds_bytes = p.lds_bytes, g->block_bytes = p.block_bytes;
-  g->device_bytes = size_t(p.blocks_per_cu) * size_t(kRefCus) * p.block_bytes + size_t(p.half) * 8u;
+  g->device_bytes = size_t(p.blocks_per_cu) * size_t(kRefCus) * p.block_bytes + size_t(p.half) * 8u + size_t(p.elev) * 8u;
 }
 
 // c_j, s_j: the angle and its cosine and sine in double, rounded to float once
@@ -96,6 +114,15 @@ inline void fill_table(const d2pc_sectors_config &c, float *cs, float *sn) {
   for (int j = 0; j < c.n_sectors / 2; ++j) {
     const double a = c.azimuth0 + two_pi * double(j) / double(c.n_sectors);
     cs[j] = float(std::cos(a)), sn[j] = float(std::sin(a));
+  }
+}
+
+// ce_i, se_i of an elevation-mode configuration: the boundary elevation and its cosine and sine in double, rounded once
+inline void fill_elevation_table(const d2pc_sectors_config &c, float *ce, float *se) {
+  const double lo = double(c.u_min), span = double(c.u_max) - double(c.u_min);
+  for (int i = 0; i <= c.n_layers; ++i) {
+    const double e = lo + (double(i) * span) / double(c.n_layers);
+    ce[i] = float(std::cos(e)), se[i] = float(std::sin(e));
   }
 }
 
@@ -146,7 +173,7 @@ struct Launch {
   Plan plan;
   const void *points;
   const uint32_t *counts;
-  const float *table;          // DEVICE: half x (c, s)
+  const float *table;          // DEVICE: half x (c, s), then plan.elev x (ce, se)
   uint64_t *slab_keys;         // DEVICE: blocks x n_cells
   uint32_t *slab_counts;       // DEVICE: blocks x n_cells
   float *range;
@@ -160,7 +187,7 @@ struct Launch {
 };
 // hipError_t as int
 int launch_sectors(const Launch &a);
-int prepare_sectors_kernels(size_t lds_bytes);   // once per session, on its device
+int prepare_sectors_kernels(const Plan &p);      // once per session, on its device
 
 }  // namespace sectors
 }  // namespace d2pc

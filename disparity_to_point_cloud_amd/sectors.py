@@ -13,11 +13,13 @@ from .capi import D2pcError
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 MAX_SECTORS, MAX_LAYERS, SHARE_POINTS = 360, 16, 1024
+MAX_ELEVATION_LAYERS = 64
+LAYERS_HEIGHT, LAYERS_ELEVATION = 0, 1   # layer_kind: height slabs and horizontal range / elevation angles and Euclidean range
 EMPTY = 0xFFFFFFFF   # `nearest` of an empty cell
 
 # every symbol include/d2pc_sectors.h declares (tests check the library exports all of them and nothing else)
 SECTORS_SYMBOLS = [
-    "d2pc_sectors_config_init", "d2pc_sectors_geometry", "d2pc_sectors_table", "d2pc_sectors_create",
+    "d2pc_sectors_config_init", "d2pc_sectors_geometry", "d2pc_sectors_table", "d2pc_sectors_elevation_table", "d2pc_sectors_create",
     "d2pc_sectors_destroy", "d2pc_sectors_last_error", "d2pc_sectors_blocks", "d2pc_sectors_desc_init",
     "d2pc_sectors_desc_check", "d2pc_sectors_process_device",
 ]
@@ -28,7 +30,7 @@ class SectorsConfig(ctypes.Structure):
         ("struct_size", ctypes.c_uint32), ("device_id", ctypes.c_int32), ("n_sectors", ctypes.c_int32),
         ("n_layers", ctypes.c_int32), ("azimuth0", ctypes.c_double), ("r_min", ctypes.c_float), ("r_max", ctypes.c_float),
         ("u_min", ctypes.c_float), ("u_max", ctypes.c_float), ("axes", ctypes.c_int32 * 3), ("min_count", ctypes.c_int32),
-        ("no_obstacle_cm", ctypes.c_uint32), ("reserved", ctypes.c_int32 * 4),
+        ("no_obstacle_cm", ctypes.c_uint32), ("layer_kind", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3),
     ]
 
 
@@ -36,7 +38,7 @@ class SectorsGeometry(ctypes.Structure):
     _fields_ = [
         ("n_cells", ctypes.c_int32), ("table_entries", ctypes.c_int32), ("rmin2", ctypes.c_float), ("rmax2", ctypes.c_float),
         ("inv_h", ctypes.c_float), ("share_points", ctypes.c_int32), ("blocks_per_cu", ctypes.c_int32),
-        ("reserved0", ctypes.c_int32), ("lds_bytes", ctypes.c_size_t), ("block_bytes", ctypes.c_size_t),
+        ("elevation_entries", ctypes.c_int32), ("lds_bytes", ctypes.c_size_t), ("block_bytes", ctypes.c_size_t),
         ("device_bytes", ctypes.c_size_t), ("reserved", ctypes.c_int32 * 4),
     ]
 
@@ -80,6 +82,8 @@ def load_sectors_library(variant=None):
     L.d2pc_sectors_config_init.restype = None
     L.d2pc_sectors_geometry.argtypes = [cfg, ctypes.POINTER(SectorsGeometry)]
     L.d2pc_sectors_table.argtypes = [cfg, fp, fp, ctypes.c_int]
+    if variant is None or hasattr(L, "d2pc_sectors_elevation_table"):   # (an A/B variant may be a build from before it)
+        L.d2pc_sectors_elevation_table.argtypes = [cfg, fp, fp, ctypes.c_int]
     L.d2pc_sectors_create.argtypes = [cfg, ctypes.POINTER(vp)]
     L.d2pc_sectors_destroy.argtypes = [vp]
     L.d2pc_sectors_last_error.argtypes = [vp]
@@ -137,6 +141,17 @@ def sectors_table(cfg: SectorsConfig):
     return c[:n].copy(), s[:n].copy()
 
 
+def sectors_elevation_table(cfg: SectorsConfig):
+    """d2pc_sectors_elevation_table: (ce, se) of the n_layers + 1 boundary elevations of an elevation-mode configuration."""
+    c = np.zeros(MAX_ELEVATION_LAYERS + 1, dtype=np.float32)
+    s = np.zeros(MAX_ELEVATION_LAYERS + 1, dtype=np.float32)
+    fp = ctypes.POINTER(ctypes.c_float)
+    n = load_sectors_library().d2pc_sectors_elevation_table(ctypes.byref(cfg), c.ctypes.data_as(fp), s.ctypes.data_as(fp), len(c))
+    if n <= 0:
+        raise D2pcError(-n, "sectors_elevation_table(%d layers, kind %d)" % (cfg.n_layers, cfg.layer_kind))
+    return c[:n].copy(), s[:n].copy()
+
+
 def sectors_desc_check(cfg: SectorsConfig, desc: SectorsDesc) -> int:
     """d2pc_sectors_desc_check: the status d2pc_sectors_process_device would refuse `desc` with (0: accepted)."""
     return load_sectors_library().d2pc_sectors_desc_check(ctypes.byref(cfg), ctypes.byref(desc))
@@ -148,7 +163,7 @@ def _ptr(x):
 
 
 class Sectors:
-    """d2pc_sectors_*: one session = one grid geometry on one device.  `process` takes torch tensors or raw device
+    """d2pc_sectors_*: one session = one grid geometry (of height or of elevation layers: `layer_kind`) on one device.  `process` takes torch tensors or raw device
     pointers, is asynchronous on `stream` and allocates nothing."""
 
     def __init__(self, cfg: SectorsConfig = None, variant=None, **kw):

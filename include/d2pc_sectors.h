@@ -55,6 +55,35 @@
  *     distance_cm  uint16   no_obstacle_cm when count < min_count, otherwise fl(range * 100.0f) truncated towards zero
  *                           and clamped to 65534 (OBSTACLE_DISTANCE's form; MAVLink asks for max_distance + 1 where
  *                           nothing is seen; marking sectors no camera covers as 65535 is the caller's)
+ *
+ * ------------------------------------------------------------------------------- ELEVATION LAYERS (layer_kind = 1)
+ * The layers above are height slabs and the range is the horizontal one: what OBSTACLE_DISTANCE asks for.  A local
+ * planner's polar histogram is azimuth x ELEVATION ANGLE (typically 60 x 30 cells of 6 degrees) and holds the Euclidean
+ * distance of the nearest point in each direction.  With layer_kind = D2PC_SECTORS_LAYERS_ELEVATION the picks, the
+ * sector, the cell's place, the empty key and the four outputs are as above; what changes is this.  tests/
+ * sectors_elev_ref.py restates it in numpy.
+ *
+ * Boundaries.  u_min and u_max are the elevation band in radians, measured from the horizontal plane towards u, both
+ * within [-1.5707964f, +1.5707964f] (the float nearest pi/2) and u_min < u_max; there is no height gate.  With n =
+ * n_layers (1 .. D2PC_SECTORS_MAX_ELEVATION_LAYERS) the n + 1 boundary elevations are, in double,
+ *     e_i = (double)u_min + ((double)i * ((double)u_max - (double)u_min)) / (double)n,   i = 0 .. n
+ * and the elevation table holds  ce_i = (float)cos(e_i),  se_i = (float)sin(e_i), evaluated in double and rounded once
+ * on the host (d2pc_sectors_elevation_table returns it).
+ *
+ * Per point.  r2 as above, then
+ *     h   = sqrtf(r2), correctly rounded            d2 = fl(r2 + fl(u*u))
+ *     t_i = fl(fl(ce_i*u) - fl(se_i*h))             (the sine of the point's elevation above boundary i, times its range)
+ *
+ * Gate.  x, y and z are finite;  r2 > 0 (a point on the vertical axis has no azimuth);  rmin2 <= d2 <= rmax2 (the range
+ * gate is on the EUCLIDEAN range; r_max = +inf is allowed, and d2 = +inf with it);  t_0 >= 0  and  not (t_n >= 0) --
+ * exactly so: a NaN t (0 * inf: h = +inf against a boundary at elevation 0) takes no part in any comparison.
+ *
+ * Layer.  The number of i in 1 .. n - 1 with t_i >= 0.  Like the sector this COUNT is the definition: it is total and
+ * needs no atan2; away from a boundary it is the layer float64 atan2(u, hypot(f, l)) binning gives.  cell = layer *
+ * n_sectors + sector, the lowest elevation first.
+ *
+ * Key.  (bits(d2) << 32) | position: the smallest Euclidean d2 and, among equal d2, the smallest position.
+ * range = sqrtf(smallest d2); count, nearest and distance_cm are formed from the key and the range exactly as above.
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -67,51 +96,62 @@ extern "C" {
 
 #define D2PC_SECTORS_MAX_SECTORS 360
 #define D2PC_SECTORS_MAX_LAYERS 16
+#define D2PC_SECTORS_MAX_ELEVATION_LAYERS 64   /* with n_sectors * n_layers <= 360 * 16 */
+#define D2PC_SECTORS_LAYERS_HEIGHT 0      /* layer_kind: height slabs, horizontal range (the default) */
+#define D2PC_SECTORS_LAYERS_ELEVATION 1   /* layer_kind: elevation-angle layers, Euclidean range */
 #define D2PC_SECTORS_SHARE_POINTS 1024   /* records one block takes per step of its walk */
 
 typedef struct d2pc_sectors_config {   /* fixed for a session */
   uint32_t struct_size;        /* sizeof(d2pc_sectors_config) */
   int32_t device_id;
   int32_t n_sectors;           /* even, 2 .. D2PC_SECTORS_MAX_SECTORS */
-  int32_t n_layers;            /* 1 .. D2PC_SECTORS_MAX_LAYERS height slabs between u_min and u_max */
+  int32_t n_layers;            /* 1 .. D2PC_SECTORS_MAX_LAYERS height slabs between u_min and u_max; elevation mode:
+                                  1 .. D2PC_SECTORS_MAX_ELEVATION_LAYERS layers, n_sectors * n_layers <= 5,760 */
   double azimuth0;             /* radians, finite: where sector 0 begins, from f towards l */
-  float r_min, r_max;          /* horizontal range gate, 0 <= r_min <= r_max; r_max may be +inf */
-  float u_min, u_max;          /* height gate u_min <= u < u_max; -inf / +inf for none when n_layers = 1 */
+  float r_min, r_max;          /* range gate (horizontal; Euclidean in elevation mode), 0 <= r_min <= r_max; r_max may be +inf */
+  float u_min, u_max;          /* height gate u_min <= u < u_max; -inf / +inf for none when n_layers = 1.  Elevation mode:
+                                  the elevation band in radians, -1.5707964f <= u_min < u_max <= 1.5707964f */
   int32_t axes[3];             /* f, l, u: +-1, +-2, +-3 of distinct magnitudes */
   int32_t min_count;           /* >= 1: cells with fewer points report no obstacle in range / distance_cm */
   uint32_t no_obstacle_cm;     /* <= 65535: distance_cm of such a cell */
-  int32_t reserved[4];         /* zero */
+  int32_t layer_kind;          /* D2PC_SECTORS_LAYERS_HEIGHT (0, the default) or D2PC_SECTORS_LAYERS_ELEVATION */
+  int32_t reserved[3];         /* zero */
 } d2pc_sectors_config;
 /* 72 x 1, azimuth0 = -pi/72 (sector 0 centred on forward), r 0.2 .. +inf, u -inf .. +inf, axes {3, -1, -2} (a camera's
- * optical frame, counter-clockwise), min_count 1, no_obstacle_cm 65535, device 0. */
+ * optical frame, counter-clockwise), min_count 1, no_obstacle_cm 65535, device 0, height layers. */
 void d2pc_sectors_config_init(d2pc_sectors_config *cfg);
 
 typedef struct d2pc_sectors_geometry_t {
   int32_t n_cells;             /* n_sectors * n_layers: entries of every output */
   int32_t table_entries;       /* n_sectors / 2 */
-  float rmin2, rmax2, inv_h;   /* as the specification forms them; inv_h is 0 when n_layers = 1 */
+  float rmin2, rmax2, inv_h;   /* as the specification forms them; inv_h is 0 when n_layers = 1 and in elevation mode */
   int32_t share_points;        /* D2PC_SECTORS_SHARE_POINTS */
   int32_t blocks_per_cu;       /* blocks of the reducing kernel per compute unit: as many as the tables in LDS allow, 4
                                   at the most; a session holds blocks_per_cu x the device's compute units of them */
-  int32_t reserved0;
-  size_t lds_bytes;            /* of one block: the cells' keys and counts and the boundary table */
+  int32_t elevation_entries;   /* n_layers + 1 in elevation mode, otherwise 0 */
+  size_t lds_bytes;            /* of one block: the cells' keys and counts, the boundary table and, behind it, the
+                                  elevation table */
   size_t block_bytes;          /* device memory the session holds PER BLOCK (its slab of partial cells); the session
-                                  adds the boundary table, 8 * table_entries bytes */
+                                  adds the two tables, 8 * (table_entries + elevation_entries) bytes */
   size_t device_bytes;         /* what a session holds on an MI355X (256 compute units) */
   int32_t reserved[4];
 } d2pc_sectors_geometry_t;
 /* Host arithmetic only, no device.  The refusals are d2pc_sectors_create's.  D2PC_ERR_INVALID_ARG: NULL, struct_size,
  * axes, an odd n_sectors or one out of range, a NaN parameter or a non-finite azimuth0, r_min < 0, r_min > r_max,
- * u_min > u_max, min_count < 1, no_obstacle_cm > 65535.  D2PC_ERR_BAD_SIZE: n_layers out of range; n_layers > 1 with a
- * non-finite or empty height band, or one so narrow or wide that inv_h is not a positive finite number. */
+ * u_min > u_max, min_count < 1, no_obstacle_cm > 65535, a layer_kind that is none.  D2PC_ERR_BAD_SIZE: n_layers out of
+ * range; n_layers > 1 with a non-finite or empty height band, or one so narrow or wide that inv_h is not a positive
+ * finite number; in elevation mode n_sectors * n_layers > 5,760, a band bound outside +-1.5707964f, u_min == u_max. */
 int d2pc_sectors_geometry(const d2pc_sectors_config *cfg, d2pc_sectors_geometry_t *out);
 /* Host only: the boundary table, c[j] and s[j] for j < n_sectors / 2.  Returns the number of entries (> 0), or the
  * negated d2pc_status: of the configuration's refusal, D2PC_ERR_INVALID_ARG for NULL, D2PC_ERR_CAPACITY when
  * capacity < n_sectors / 2. */
 int d2pc_sectors_table(const d2pc_sectors_config *cfg, float *c, float *s, int capacity);
+/* Host only: the elevation table, c[i] = ce_i and s[i] = se_i for i <= n_layers.  Returns n_layers + 1 or the negated
+ * d2pc_status as d2pc_sectors_table does; D2PC_ERR_INVALID_ARG for a configuration of height layers (it has none). */
+int d2pc_sectors_elevation_table(const d2pc_sectors_config *cfg, float *c, float *s, int capacity);
 
 typedef struct d2pc_sectors d2pc_sectors;
-/* Allocates everything the session will ever need (the table and the blocks' slabs): d2pc_sectors_process_device
+/* Allocates everything the session will ever need (the tables and the blocks' slabs): d2pc_sectors_process_device
  * allocates nothing.  D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
 int d2pc_sectors_create(const d2pc_sectors_config *cfg, d2pc_sectors **out);
 int d2pc_sectors_destroy(d2pc_sectors *s);

@@ -18,6 +18,13 @@ ranks them).  GPU box only.
                                             SDEFS=-DD2PC_SECTORS_FORCE_ROUNDS=0`; the product picks by the grid's size), on a
                                             cloud in producer order and on the same cloud shuffled, for the smallest and the
                                             largest grid
+  python tools/sectors_bench.py --elevation [--parent NAME]
+                                        ->  profiles/sectors_elevation_bench.txt: elevation layers (layer_kind 1) beside height
+                                            layers on the rig's merged cloud, S / S0 / C of 72 x 16 height, 72 x 16 elevation and
+                                            60 x 30 elevation in ONE interleaved run; with --parent NAME also the height rows
+                                            72 x 1 and 360 x 16 of this build against libd2pc_sectors_NAME.so, a build of the
+                                            sources before the elevation layers (`make sectors SNAME=NAME` there): the height
+                                            instantiation may not be slower than it by more than the arms' spread
 """
 import argparse
 import os
@@ -221,16 +228,96 @@ def ab(a):
     return lines
 
 
+def elevation(a):
+    """Elevation layers beside height layers, and this build's height rows beside an earlier build's."""
+    prop = torch.cuda.get_device_properties(0)
+    half_pi = float(np.float32(np.pi / 2))
+    grids = [("72 x 16 height", dict(n_sectors=72, n_layers=16, u_min=-40.0, u_max=40.0)),
+             ("72 x 16 elevation", dict(n_sectors=72, n_layers=16, u_min=-half_pi, u_max=half_pi, layer_kind=d2pc.LAYERS_ELEVATION)),
+             ("60 x 30 elevation", dict(n_sectors=60, n_layers=30, u_min=-half_pi, u_max=half_pi, azimuth0=-np.pi / 60,
+                                        layer_kind=d2pc.LAYERS_ELEVATION))]
+    versus = [("72 x 1 height", dict()), ("360 x 16 height", dict(n_sectors=360, n_layers=16, u_min=-40.0, u_max=40.0))]
+    lines = ["# tools/sectors_bench.py --elevation%s --rounds %d --iters %d" % (" --parent " + a.parent if a.parent else "", a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round)" % (
+                 prop.name, prop.multi_processor_count),
+             "# the 16-camera rig's merged cloud; S = d2pc_sectors_process_device alone (two launches, range + count); S0 = the same with",
+             "# a count of 0; C = d2pc_membench_copy moving the bytes S reads (16 B per point).  us per call: median (min .. max)"]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    name, n, w, h, mode, rig_case, holes = CASES[1]
+    with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx:
+        prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+        prod(s)
+        torch.cuda.synchronize()
+        npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n])
+        cloud = prod.pts[:npts].clone()
+        zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+        half = max(16 * npts // 2 // 16 * 16, 16)
+        src = torch.empty(half, dtype=torch.uint8, device="cuda")
+        dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+        sessions, arms, labels = [], [lambda: ctx.membench_copy(src.data_ptr(), dst.data_ptr(), half, s)], ["C"]
+
+        def add(label, grid, variant=None, empty=False):
+            sec = d2pc.Sectors(variant=variant, **grid)
+            out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
+                       count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+            sessions.append((sec, out))
+            arms.append(lambda: sec.process(cloud, npts, stream_ptr=s, **out))
+            labels.append(label)
+            if empty:
+                arms.append(lambda: sec.process(cloud, npts, counts=zero, stream_ptr=s, **out))
+                labels.append(label + " S0")
+
+        for label, grid in grids:
+            add(label, grid, empty=True)
+        for label, grid in versus if a.parent else []:
+            add(label + " new", grid)
+            add(label + " parent", grid, variant=a.parent)
+        for fn in arms:   # warm-up: code objects
+            fn()
+        torch.cuda.synchronize()
+        if a.parent:   # the two builds compute the same bytes
+            for i in range(len(grids), len(sessions), 2):
+                assert all(torch.equal(sessions[i][1][k], sessions[i + 1][1][k]) for k in ("range", "count")), "the builds disagree"
+        iters = int(min(max(a.iters, 30000.0 / timed(arms[1], 5)), 4000))
+        t = dict(zip(labels, interleaved(arms, a.rounds, iters)))
+        ctx.check_async_error()
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        lines.append("# %d points, %.1f MB read, %d calls per timed window" % (npts, 16 * npts / 1e6, iters))
+        lines.append("%-20s %8s %10s %-30s %-30s %-30s %6s" % ("grid", "cells", "LDS B", "S", "S0", "C", "S/C"))
+        for (label, grid), (sec, _) in zip(grids, sessions):
+            lines.append("%-20s %8d %10d %-30s %-30s %-30s %6.2f" % (label, sec.n_cells, sec.geometry.lds_bytes, fmt(t[label]), fmt(t[label + " S0"]),
+                                                                   fmt(t["C"]), med[label] / med["C"]))
+        if a.parent:
+            lines.append("# the height instantiation against libd2pc_sectors_%s.so: new may be slower by no more than the larger of the two arms'" % a.parent)
+            lines.append("# (max - min) / median in this run")
+            lines.append("%-20s %-30s %-30s %10s %10s %s" % ("grid", "new", "parent", "new/parent", "allowed", "verdict"))
+            for label, _ in versus:
+                new, old = t[label + " new"], t[label + " parent"]
+                spread = max((max(v) - min(v)) / float(np.median(v)) for v in (new, old))
+                ratio = med[label + " new"] / med[label + " parent"]
+                lines.append("%-20s %-30s %-30s %10.4f %10.4f %s" % (label, fmt(new), fmt(old), ratio, 1.0 + spread,
+                                                                     "ok" if ratio <= 1.0 + spread else "SLOWER"))
+        for sec, _ in sessions:
+            sec.close()
+        prod.close()
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", type=int, default=None, help="one case only, by its index (a profiler run)")
     ap.add_argument("--ab", action="store_true", help="the A/B of the in-wave reduction instead of the cost table")
+    ap.add_argument("--elevation", action="store_true", help="elevation layers beside height layers instead of the cost table")
+    ap.add_argument("--parent", default=None, help="with --elevation: libd2pc_sectors_<PARENT>.so, an earlier build, for the height rows")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    out = a.out or os.path.join(ROOT, "profiles", "sectors_ab.txt" if a.ab else "sectors_bench.txt")
-    lines = ab(a) if a.ab else bench(a)
+    out = a.out or os.path.join(ROOT, "profiles", "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_bench.txt")
+    lines = elevation(a) if a.elevation else ab(a) if a.ab else bench(a)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -22,7 +22,11 @@ SECTORS_SYMBOLS = [
     "d2pc_sectors_config_init", "d2pc_sectors_geometry", "d2pc_sectors_table", "d2pc_sectors_elevation_table", "d2pc_sectors_create",
     "d2pc_sectors_destroy", "d2pc_sectors_last_error", "d2pc_sectors_blocks", "d2pc_sectors_desc_init",
     "d2pc_sectors_desc_check", "d2pc_sectors_process_device",
+    "d2pc_sectors_memory_create", "d2pc_sectors_memory_destroy", "d2pc_sectors_memory_last_error", "d2pc_sectors_memory_desc_init",
+    "d2pc_sectors_memory_desc_check", "d2pc_sectors_memory_update_device", "d2pc_sectors_memory_reset_device",
+    "d2pc_sectors_memory_coverage",
 ]
+EMPTY_AGE, OLDEST_AGE = 0xFFFFFFFF, 0xFFFFFFFE   # the age word of an empty record; where an age saturates
 
 
 class SectorsConfig(ctypes.Structure):
@@ -49,6 +53,29 @@ class SectorsDesc(ctypes.Structure):
         ("reserved", ctypes.c_int32), ("points", ctypes.c_void_p), ("counts", ctypes.c_void_p),
         ("cloud_points", ctypes.c_size_t), ("points_frame_stride_points", ctypes.c_size_t), ("range", ctypes.c_void_p),
         ("count", ctypes.c_void_p), ("nearest", ctypes.c_void_p), ("distance_cm", ctypes.c_void_p),
+    ]
+
+
+class SectorsMemoryConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_age", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class SectorsMemoryStep(ctypes.Structure):   # 64 bytes, in device memory
+    _fields_ = [("R", ctypes.c_float * 9), ("t", ctypes.c_float * 3), ("dt", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class SectorsFov(ctypes.Structure):
+    _fields_ = [("yaw", ctypes.c_double), ("pitch", ctypes.c_double), ("h_fov", ctypes.c_double), ("v_fov", ctypes.c_double),
+                ("margin", ctypes.c_double)]
+
+
+class SectorsMemoryDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("point_step", ctypes.c_int32), ("n_clouds", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("points", ctypes.c_void_p), ("cloud_points", ctypes.c_size_t),
+        ("points_frame_stride_points", ctypes.c_size_t), ("count", ctypes.c_void_p), ("nearest", ctypes.c_void_p),
+        ("step", ctypes.c_void_p), ("covered", ctypes.c_void_p), ("range", ctypes.c_void_p), ("distance_cm", ctypes.c_void_p),
+        ("age", ctypes.c_void_p), ("records", ctypes.c_void_p),
     ]
 
 
@@ -93,6 +120,18 @@ def load_sectors_library(variant=None):
     L.d2pc_sectors_desc_init.restype = None
     L.d2pc_sectors_desc_check.argtypes = [cfg, desc]
     L.d2pc_sectors_process_device.argtypes = [vp, desc, vp]
+    if variant is None or hasattr(L, "d2pc_sectors_memory_create"):   # (an A/B variant may be a build from before the memory)
+        mcfg, mdesc = ctypes.POINTER(SectorsMemoryConfig), ctypes.POINTER(SectorsMemoryDesc)
+        L.d2pc_sectors_memory_create.argtypes = [cfg, mcfg, ctypes.POINTER(vp)]
+        L.d2pc_sectors_memory_destroy.argtypes = [vp]
+        L.d2pc_sectors_memory_last_error.argtypes = [vp]
+        L.d2pc_sectors_memory_last_error.restype = ctypes.c_char_p
+        L.d2pc_sectors_memory_desc_init.argtypes = [mdesc]
+        L.d2pc_sectors_memory_desc_init.restype = None
+        L.d2pc_sectors_memory_desc_check.argtypes = [cfg, mcfg, mdesc]
+        L.d2pc_sectors_memory_update_device.argtypes = [vp, mdesc, vp]
+        L.d2pc_sectors_memory_reset_device.argtypes = [vp, vp]
+        L.d2pc_sectors_memory_coverage.argtypes = [cfg, ctypes.POINTER(SectorsFov), ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]
     if variant is None:
         _lib = L
     return L
@@ -214,3 +253,102 @@ class Sectors:
             point_step=point_step, n_clouds=n_clouds, points=_ptr(points), counts=_ptr(counts), cloud_points=cloud_points,
             points_frame_stride_points=frame_stride_points, range=_ptr(range), count=_ptr(count), nearest=_ptr(nearest),
             distance_cm=_ptr(distance_cm)), stream_ptr)
+
+
+def sectors_memory_config(max_age=OLDEST_AGE) -> SectorsMemoryConfig:
+    """A d2pc_sectors_memory_config with its struct_size and `max_age` ticks."""
+    return SectorsMemoryConfig(struct_size=ctypes.sizeof(SectorsMemoryConfig), max_age=max_age)
+
+
+def sectors_memory_desc_init(**kw) -> SectorsMemoryDesc:
+    """d2pc_sectors_memory_desc_init, then the given fields."""
+    d = SectorsMemoryDesc()
+    load_sectors_library().d2pc_sectors_memory_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_memory_desc_check(cfg: SectorsConfig, mcfg: SectorsMemoryConfig, desc: SectorsMemoryDesc) -> int:
+    """d2pc_sectors_memory_desc_check: the status d2pc_sectors_memory_update_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_memory_desc_check(ctypes.byref(cfg), ctypes.byref(mcfg), ctypes.byref(desc))
+
+
+def sectors_memory_step(R, t, dt) -> np.ndarray:
+    """The 16 words of a d2pc_sectors_memory_step (R row-major, t, dt, three zeros) as uint32, to copy to the device."""
+    w = np.zeros(16, dtype=np.uint32)
+    w[:9] = np.asarray(R, dtype=np.float32).reshape(9).view(np.uint32)
+    w[9:12] = np.asarray(t, dtype=np.float32).reshape(3).view(np.uint32)
+    w[12] = dt
+    return w
+
+
+def sectors_memory_coverage(cfg: SectorsConfig, fovs) -> np.ndarray:
+    """d2pc_sectors_memory_coverage: uint8 per cell, 1 where a field of view of `fovs` (SectorsFov, or (yaw, pitch, h_fov,
+    v_fov, margin) tuples) holds the cell's centre direction."""
+    fovs = [f if isinstance(f, SectorsFov) else SectorsFov(*f) for f in fovs]
+    arr = (SectorsFov * max(len(fovs), 1))(*fovs)
+    out = np.zeros(MAX_SECTORS * MAX_LAYERS, dtype=np.uint8)
+    n = load_sectors_library().d2pc_sectors_memory_coverage(ctypes.byref(cfg), arr, len(fovs),
+                                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(out))
+    if n <= 0:
+        raise D2pcError(-n, "sectors_memory_coverage(%d x %d)" % (cfg.n_sectors, cfg.n_layers))
+    return out[:n].copy()
+
+
+class SectorsMemory:
+    """d2pc_sectors_memory_*: one world-frame point per cell of a grid, kept on the device between calls.  `update` takes
+    torch tensors or raw device pointers, is asynchronous on `stream` and allocates nothing."""
+
+    def __init__(self, cfg: SectorsConfig, max_age=OLDEST_AGE):
+        self._L, self._h = load_sectors_library(), None
+        self.cfg, self.mcfg = cfg, sectors_memory_config(max_age)
+        h = ctypes.c_void_p()
+        st = self._L.d2pc_sectors_memory_create(ctypes.byref(self.cfg), ctypes.byref(self.mcfg), ctypes.byref(h))
+        if st:
+            raise D2pcError(st, "sectors_memory_create(%d x %d, max_age %d)" % (cfg.n_sectors, cfg.n_layers, max_age))
+        self._h = h
+        self.n_cells = cfg.n_sectors * cfg.n_layers
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.d2pc_sectors_memory_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def last_error(self) -> str:
+        return self._L.d2pc_sectors_memory_last_error(self._h).decode()
+
+    def update_desc(self, desc: SectorsMemoryDesc, stream_ptr=None):
+        """d2pc_sectors_memory_update_device."""
+        st = self._L.d2pc_sectors_memory_update_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def update(self, points, cloud_points, count, nearest, step, point_step=16, n_clouds=1, frame_stride_points=0, covered=None,
+               range=None, distance_cm=None, age=None, records=None, stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.update_desc(sectors_memory_desc_init(
+            point_step=point_step, n_clouds=n_clouds, points=_ptr(points), cloud_points=cloud_points,
+            points_frame_stride_points=frame_stride_points, count=_ptr(count), nearest=_ptr(nearest), step=_ptr(step),
+            covered=_ptr(covered), range=_ptr(range), distance_cm=_ptr(distance_cm), age=_ptr(age), records=_ptr(records)),
+            stream_ptr)
+
+    def reset(self, stream_ptr=None):
+        """d2pc_sectors_memory_reset_device."""
+        st = self._L.d2pc_sectors_memory_reset_device(self._h, stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())

@@ -84,6 +84,43 @@
  *
  * Key.  (bits(d2) << 32) | position: the smallest Euclidean d2 and, among equal d2, the smallest position.
  * range = sqrtf(smallest d2); count, nearest and distance_cm are formed from the key and the range exactly as above.
+ *
+ * ------------------------------------------------------------------------------------- MEMORY (d2pc_sectors_memory_*)
+ * One forward camera fills a few cells of a 360-degree grid; a wall the vehicle yawed away from is gone one frame later.
+ * A memory session keeps ONE point per cell in a fixed (world) frame between calls, as a local planner's histogram
+ * memory does.  d2pc_sectors_memory_update_device takes what d2pc_sectors_process_device wrote for a cloud (count,
+ * nearest), the cloud and a pose, re-bins the remembered points under the new pose, ages them and merges them with the
+ * cells seen now.  The gate, layer, sector and cell of a remembered point are the definitions above, with the same
+ * tables and the same comparisons: it lands in exactly the cell the grid itself would put it in.
+ * tests/sectors_memory_ref.py restates this in numpy.
+ *
+ * A record is 16 bytes: the world x, y, z as float32 and the age as uint32, in the caller's ticks.  The empty record is
+ * the words 0, 0, 0, 0xFFFFFFFF.  The step (d2pc_sectors_memory_step, in DEVICE memory) holds R (row-major), t and dt:
+ * world = R p + t for a point p in the frame of `points`; dt is the ticks since the previous update.
+ *
+ * Carry.  For every non-empty remembered record i (world w, age a):
+ *     1. a' = min(a + dt, 0xFFFFFFFE), formed without wrap; the record is dropped if a' > max_age
+ *     2. d = (fl(w.x - t.x), fl(w.y - t.y), fl(w.z - t.z))
+ *     3. p.x = fl(fl(fl(R[0]*d.x) + fl(R[3]*d.y)) + fl(R[6]*d.z)),  p.y likewise with R[1], R[4], R[7],  p.z with R[2],
+ *        R[5], R[8]: the transpose of R
+ *     4. p goes through the gate, layer and sector of the session's layer kind exactly as a record x, y, z above does
+ *        (the picks, the tables, every comparison); it is dropped if it takes no part
+ *     5. it is dropped if `covered` is given and covered[cell] != 0
+ *     6. otherwise the cell's carry key is the minimum, as an unsigned 64-bit number, of (bits(k) << 32) | i with k = r2
+ *        for height layers and k = d2 for elevation layers
+ *
+ * Merge, per cell c.  The cell is FRESH when count[c] >= min_count and nearest[c] is below the call's position bound
+ * (n_clouds - 1) * points_frame_stride_points + cloud_points (cloud_points for one cloud).  A `nearest` at or above the
+ * bound counts as not seen; nothing is read there.
+ *     fresh              q = the record at position nearest[c].  The new record is
+ *                        (fl(fl(fl(fl(R[0]*q.x) + fl(R[1]*q.y)) + fl(R[2]*q.z)) + t.x), likewise with R[3..5] and t.y,
+ *                        with R[6..8] and t.z, age 0) and range = sqrtf(k(q)) with k formed from the picks of q as
+ *                        above: the bits d2pc_sectors_process_device wrote to range[c]
+ *     not fresh, a key   the new record is record i (the key's low word) unchanged with the age a';
+ *                        range = sqrtf(the key's high word).  min_count does not apply to a remembered cell
+ *     otherwise          the empty record; range = +inf
+ * distance_cm is formed from range as above, no_obstacle_cm where the record is empty; age[c] is the record's age word.
+ * The new records replace the old as one step: no carry reads a record this call wrote.
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -193,6 +230,82 @@ int d2pc_sectors_desc_check(const d2pc_sectors_config *cfg, const d2pc_sectors_d
  * The slabs belong to the session: one launch of a session in flight per stream order; two streams need two sessions.
  */
 int d2pc_sectors_process_device(d2pc_sectors *s, const d2pc_sectors_desc *desc, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------- the memory */
+typedef struct d2pc_sectors_memory_config {   /* fixed for a memory session, beside the grid's d2pc_sectors_config */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_memory_config) */
+  uint32_t max_age;            /* <= 0xFFFFFFFE, in the caller's ticks (say milliseconds): a record older than this is dropped */
+  uint32_t reserved[2];        /* zero */
+} d2pc_sectors_memory_config;
+
+typedef struct d2pc_sectors_memory_step {   /* 64 bytes in DEVICE memory: a captured graph replays with a new pose after one small copy */
+  float R[9];                  /* row-major: world = R p + t for a point p in the frame of `points` */
+  float t[3];
+  uint32_t dt;                 /* ticks since the previous update */
+  uint32_t reserved[3];
+} d2pc_sectors_memory_step;
+
+typedef struct d2pc_sectors_fov {   /* radians; yaw from f towards l, as azimuth0 is; pitch from the horizontal plane towards u */
+  double yaw, pitch, h_fov, v_fov, margin;
+} d2pc_sectors_fov;
+
+typedef struct d2pc_sectors_memory d2pc_sectors_memory;
+/* Takes the grid's configuration (either layer kind) and refuses what d2pc_sectors_create refuses, with its statuses;
+ * then D2PC_ERR_INVALID_ARG for a NULL or wrongly sized `mcfg` or a max_age of 0xFFFFFFFF.  Allocates everything once
+ * (two record buffers of n_cells x 16 bytes, a parity word, the tables) and leaves the memory empty. */
+int d2pc_sectors_memory_create(const d2pc_sectors_config *grid, const d2pc_sectors_memory_config *mcfg, d2pc_sectors_memory **out);
+int d2pc_sectors_memory_destroy(d2pc_sectors_memory *m);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_memory_last_error(const d2pc_sectors_memory *m);
+
+typedef struct d2pc_sectors_memory_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_memory_desc) */
+  int32_t point_step;          /* 16 or 32, as d2pc_sectors_desc */
+  int32_t n_clouds;            /* 1 .. 65,535 */
+  int32_t reserved;            /* zero */
+  const void *points;          /* DEVICE: the records the sectors call read, 16-byte aligned */
+  size_t cloud_points;         /* as d2pc_sectors_desc: they give the position bound */
+  size_t points_frame_stride_points;
+  const uint32_t *count;       /* DEVICE: as d2pc_sectors_process_device wrote them for these points and this grid */
+  const uint32_t *nearest;     /* DEVICE: likewise */
+  const d2pc_sectors_memory_step *step;   /* DEVICE, 4-byte aligned */
+  const uint8_t *covered;      /* DEVICE, nullable: one byte per cell, nonzero = the cameras look there now (a remembered
+                                  point that re-bins into such a cell is dropped) */
+  float *range;                /* DEVICE out, nullable; at least one of the four is given */
+  uint16_t *distance_cm;
+  uint32_t *age;               /* the record's age word: 0 for a fresh cell, 0xFFFFFFFF for an empty one */
+  void *records;               /* n_cells x 16 bytes (world x, y, z as float32, age as uint32), 16-byte aligned */
+} d2pc_sectors_memory_desc;
+/* struct_size, point_step 16, n_clouds 1; everything else zero. */
+void d2pc_sectors_memory_desc_init(d2pc_sectors_memory_desc *desc);
+/* Host only: what d2pc_sectors_memory_update_device refuses of `desc`, without a session; first the refusals of `grid`
+ * and `mcfg` as d2pc_sectors_memory_create makes them.  D2PC_ERR_INVALID_ARG: NULL, struct_size, point_step, n_clouds,
+ * a NULL points / count / nearest / step, no output, points or records not 16-byte aligned, another pointer not
+ * aligned to its type, an output that overlaps points, count, nearest, step, covered or another output.
+ * D2PC_ERR_BAD_SIZE: cloud_points, the frame stride and the largest position as d2pc_sectors_desc_check refuses them. */
+int d2pc_sectors_memory_desc_check(const d2pc_sectors_config *grid, const d2pc_sectors_memory_config *mcfg,
+                                   const d2pc_sectors_memory_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): ONE launch of one block, no memset, no allocation, no host
+ * read -- it can be captured into a graph behind d2pc_sectors_process_device.  Every refusal is made before anything is
+ * enqueued.  The session holds two record buffers and a parity word in device memory: the launch reads one buffer,
+ * writes the other and flips the word last, on the device, so a replayed graph advances the memory as plain calls do.
+ * Bit-reproducible: every minimum is of integers.  One update of a session in flight per stream order.
+ */
+int d2pc_sectors_memory_update_device(d2pc_sectors_memory *m, const d2pc_sectors_memory_desc *desc, void *stream);
+/* Asynchronous: empties the memory with one launch (no memset node). */
+int d2pc_sectors_memory_reset_device(d2pc_sectors_memory *m, void *stream);
+/*
+ * Host only: which cells the cameras look at, for `covered`.  A cell is covered when its centre direction passes, for
+ * some FOV, in double:  |wrap(az_c - yaw)| <= h_fov / 2 - margin  and, for elevation layers,
+ * |el_c - pitch| <= v_fov / 2 - margin;  az_c = azimuth0 + 2 pi (k + 1/2) / n_sectors,  el_c = (e_i + e_{i+1}) / 2,
+ * wrap(x) = the IEEE remainder of x by 2 pi.  Height layers: the azimuth test alone, every layer alike.
+ * Writes n_cells bytes (1 or 0) and returns n_cells, or the negated d2pc_status: of the configuration's refusal,
+ * D2PC_ERR_INVALID_ARG for a NULL `covered_host`, n_fovs < 0 or NULL `fovs` with n_fovs > 0, D2PC_ERR_CAPACITY when
+ * capacity < n_cells.
+ */
+int d2pc_sectors_memory_coverage(const d2pc_sectors_config *grid, const d2pc_sectors_fov *fovs, int n_fovs,
+                                 uint8_t *covered_host, int capacity);
 
 #ifdef __cplusplus
 }

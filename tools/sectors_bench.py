@@ -25,6 +25,12 @@ ranks them).  GPU box only.
                                             72 x 1 and 360 x 16 of this build against libd2pc_sectors_NAME.so, a build of the
                                             sources before the elevation layers (`make sectors SNAME=NAME` there): the height
                                             instantiation may not be slower than it by more than the arms' spread
+  python tools/sectors_bench.py --memory
+                                        ->  profiles/sectors_memory_bench.txt: the memory (d2pc_sectors_memory_update_device, one
+                                            launch of one block) behind the sectors: M = the update alone, SM = the sectors call +
+                                            the update, beside S and S0 of the same session, on the one-camera frame and on the
+                                            rig's merged cloud, for 72 x 1 and 60 x 30 elevation, in ONE interleaved run.  No time
+                                            is fixed in advance: the yardstick is S0, the sectors' own fixed part, in the same run
 """
 import argparse
 import os
@@ -306,6 +312,87 @@ def elevation(a):
     return lines
 
 
+def memory(a):
+    """The memory's update beside the sectors call it follows, all arms of all rows interleaved in one run."""
+    prop = torch.cuda.get_device_properties(0)
+    half_pi = float(np.float32(np.pi / 2))
+    grids = [("72 x 1", dict()),
+             ("60 x 30 elevation", dict(n_sectors=60, n_layers=30, u_min=-half_pi, u_max=half_pi, azimuth0=-np.pi / 60,
+                                        layer_kind=d2pc.LAYERS_ELEVATION))]
+    lines = ["# tools/sectors_bench.py --memory --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round)" % (
+                 prop.name, prop.multi_processor_count),
+             "# S = d2pc_sectors_process_device alone (two launches; range, count, nearest); S0 = the same with every count 0;",
+             "# M = d2pc_sectors_memory_update_device alone (one launch of one block; range, distance_cm, age; a 37-degree yaw, a",
+             "# translation and dt 50 every call, max_age 2,000, a forward field of view as `covered`); SM = S then M on one stream.",
+             "# us per call: median (min .. max) over the rounds.  No time was fixed in advance: M is read against S0 of its row"]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    clouds, keep = [], []
+    for name, n, w, h, mode, rig_case, holes in CASES[:2]:
+        with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx:
+            prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+            prod(s)
+            torch.cuda.synchronize()
+            ctx.check_async_error()
+            npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n]) if rig_case else int(prod.counts.cpu().numpy().view(np.uint32)[0])
+            clouds.append((name, npts, prod.pts[:npts].clone()))
+            prod.close()
+    R = np.array([[np.cos(0.6458), 0.0, np.sin(0.6458)], [0.0, 1.0, 0.0], [-np.sin(0.6458), 0.0, np.cos(0.6458)]])   # about the optical y
+    step = torch.from_numpy(d2pc.sectors_memory_step(R, [0.4, -0.1, 0.9], 50).view(np.int32).copy()).to("cuda")
+    arms, labels, rows = [], [], []
+    for cname, npts, cloud in clouds:
+        zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+        for gname, grid in grids:
+            sec = d2pc.Sectors(**grid)
+            mem = d2pc.SectorsMemory(sec.cfg, 2000)
+            cov = torch.from_numpy(d2pc.sectors_memory_coverage(sec.cfg, [(0.0, 0.0, 1.5, 1.0, 0.05)])).to("cuda")
+            so = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
+                      count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                      nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+            mo = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
+                      distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"),
+                      age=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+            so0 = {k: torch.empty_like(v) for k, v in so.items()}   # S0's own: M reads a full cloud's count / nearest from `so`
+            keep.append((sec, mem, cov, so, so0, mo, zero))
+
+            def sectors(sec=sec, cloud=cloud, npts=npts, so=so):
+                sec.process(cloud, npts, stream_ptr=s, **so)
+
+            def empty(sec=sec, cloud=cloud, npts=npts, so0=so0, zero=zero):
+                sec.process(cloud, npts, counts=zero, stream_ptr=s, **so0)
+
+            def update(mem=mem, cloud=cloud, npts=npts, so=so, mo=mo, cov=cov):
+                mem.update(cloud, npts, so["count"], so["nearest"], step, covered=cov, stream_ptr=s, **mo)
+
+            def both(sectors=sectors, update=update):
+                sectors()
+                update()
+
+            row = "%s, %s" % (cname, gname)
+            rows.append((row, npts, sec.n_cells))
+            arms += [sectors, empty, update, both]
+            labels += [row + " " + k for k in ("S", "S0", "M", "SM")]
+    for fn in arms:   # warm-up: code objects
+        fn()
+    torch.cuda.synchronize()
+    iters = int(min(max(a.iters, 30000.0 / timed(arms[3], 5)), 4000))
+    t = dict(zip(labels, interleaved(arms, a.rounds, iters)))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    lines.append("# %d calls per timed window" % iters)
+    lines.append("%-62s %10s %6s %-30s %-30s %-30s %-30s %6s %8s" % ("cloud, grid", "points", "cells", "S", "S0", "M", "SM", "M/S0", "SM-S"))
+    for row, npts, cells in rows:
+        lines.append("%-62s %10d %6d %-30s %-30s %-30s %-30s %6.2f %8.1f" % (
+            row, npts, cells, fmt(t[row + " S"]), fmt(t[row + " S0"]), fmt(t[row + " M"]), fmt(t[row + " SM"]),
+            med[row + " M"] / med[row + " S0"], med[row + " SM"] - med[row + " S"]))
+    for sec, mem, *_ in keep:
+        mem.close()
+        sec.close()
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -313,11 +400,12 @@ def main():
     ap.add_argument("--only", type=int, default=None, help="one case only, by its index (a profiler run)")
     ap.add_argument("--ab", action="store_true", help="the A/B of the in-wave reduction instead of the cost table")
     ap.add_argument("--elevation", action="store_true", help="elevation layers beside height layers instead of the cost table")
+    ap.add_argument("--memory", action="store_true", help="the memory's update beside the sectors call instead of the cost table")
     ap.add_argument("--parent", default=None, help="with --elevation: libd2pc_sectors_<PARENT>.so, an earlier build, for the height rows")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    out = a.out or os.path.join(ROOT, "profiles", "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_bench.txt")
-    lines = elevation(a) if a.elevation else ab(a) if a.ab else bench(a)
+    out = a.out or os.path.join(ROOT, "profiles", "sectors_memory_bench.txt" if a.memory else "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_bench.txt")
+    lines = memory(a) if a.memory else elevation(a) if a.elevation else ab(a) if a.ab else bench(a)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -31,6 +31,13 @@ namespace {
 
 bool cfg_ok(const d2pc_fusion_node_config *c) { return c && c->struct_size == sizeof(d2pc_fusion_node_config); }
 
+// 64-bit: |INT_MIN| has no int
+bool offsets_refused(const d2pc_fusion_node_config &c) {
+  const int64_t ax = c.offset_x < 0 ? -int64_t(c.offset_x) : int64_t(c.offset_x);
+  const int64_t ay = c.offset_y < 0 ? -int64_t(c.offset_y) : int64_t(c.offset_y);
+  return ax > ay;
+}
+
 int geometry(const d2pc_fusion_node_config &c, d2pc_fusion_node_geometry_t *g) {
   memset(g, 0, sizeof *g);
   if (c.rule < 0 || c.rule >= FUSE_RULE_COUNT) return D2PC_ERR_INVALID_ARG;
@@ -38,6 +45,13 @@ int geometry(const d2pc_fusion_node_config &c, d2pc_fusion_node_geometry_t *g) {
   if (c.cols <= 0 || c.rows <= 0 || c.batch < 1 || c.batch > 65535) return D2PC_ERR_BAD_SIZE;
   if (c.crop_left < 0 || c.crop_right < 0 || c.crop_top < 0 || c.crop_bottom < 0) return D2PC_ERR_BAD_SIZE;
   int n1 = 0, n2 = 0;
+  // publishFusedDepthMap re-crops the incoming frame with cropToSquare(image) (:106): its arguments are 0 but the side
+  // still uses the member offset_y_ (:253), so that square has min(cols, rows) - |offset_y| pixels a side while the
+  // loop of :115-123 fuses only min(cols, rows) - max(|offset_x|, |offset_y|) of them.  With |offset_x| > |offset_y|
+  // the reference therefore publishes a larger fused map whose last rows and columns are raw, unrotated camera-2
+  // pixels run through the median (200 x 140 with 9 / -6: 94 x 94 where the fused square gives 91 x 91).  Not
+  // reproduced: refused.
+  if (offsets_refused(c)) return D2PC_ERR_BAD_SIZE;
   // camera 1: cropToSquare(image, offset_x, offset_y); camera 2: of the ROTATED image (rows x cols) with the negated
   // offsets -- while the side length still uses the member offset_y_ (:253)
   if (d2pc_crop_to_square(c.cols, c.rows, c.offset_x, c.offset_y, c.offset_y, &g->x1, &g->y1, &n1) != D2PC_OK ||
@@ -194,6 +208,9 @@ int d2pc_fusion_node_create(d2pc_ctx *ctx, const d2pc_fusion_node_config *cfg, d
   if (!cfg_ok(cfg)) return fail(ctx, D2PC_ERR_INVALID_ARG, "bad d2pc_fusion_node_config");
   d2pc_fusion_node_geometry_t g;
   const int st = geometry(*cfg, &g);
+  if (st == D2PC_ERR_BAD_SIZE && offsets_refused(*cfg))
+    return fail(ctx, st, "fusion node %dx%d: |offset_x| (%d) exceeds |offset_y| (%d): the reference fuses a smaller square than it "
+                "publishes there; not supported", cfg->cols, cfg->rows, cfg->offset_x, cfg->offset_y);
   if (st != D2PC_OK)
     return fail(ctx, st, "fusion node %dx%d offsets %d/%d: bad configuration or a square too small for the filter and the crop",
                 cfg->cols, cfg->rows, cfg->offset_x, cfg->offset_y);

@@ -42,6 +42,13 @@ class FusionNode:
         self.ctx, self.cols, self.rows, self.batch = ctx, int(cols), int(rows), int(batch)
         self.rule, self.form = rule, form
         self.device = torch.device(device)
+        # publishFusedDepthMap re-crops its frame with the side min(cols, rows) - |offset_y| (:106, :253) and fuses only
+        # min(cols, rows) - max(|offset_x|, |offset_y|) of it: with |offset_x| > |offset_y| the reference publishes a
+        # larger fused map with a margin of raw camera-2 pixels.  Refused, as d2pc_fusion_node_geometry refuses it
+        # (D2PC_ERR_BAD_SIZE)
+        if abs(offset_x) > abs(offset_y):
+            raise capi.D2pcError(3, "fusion node %dx%d: |offset_x| (%d) exceeds |offset_y| (%d): not supported"
+                                 % (self.cols, self.rows, offset_x, offset_y))
         # camera 1: cropToSquare(image, offset_x, offset_y); camera 2: of the ROTATED image (rows x cols) with the
         # negated offsets -- while the side length still uses the member offset_y_ (:253)
         self.sq1 = capi.crop_to_square(self.cols, self.rows, offset_x, offset_y)

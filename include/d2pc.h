@@ -612,7 +612,10 @@ typedef struct d2pc_fusion_node_geometry_t {
 } d2pc_fusion_node_geometry_t;
 
 /* Host arithmetic only (no context, no device).  D2PC_ERR_BAD_SIZE when a square leaves its frame, the two squares
- * differ in size, n < 11 (the score filter's halo) or the crop leaves nothing of the fused map. */
+ * differ in size, n < 11 (the score filter's halo) or the crop leaves nothing of the fused map -- and when
+ * |offset_x| > |offset_y|: there the reference re-crops the frame it fuses into with a side of min(cols, rows) -
+ * |offset_y| (:106, :253) but fuses only min(cols, rows) - max(|offset_x|, |offset_y|) of it, and publishes a larger
+ * fused map with a margin of raw camera-2 pixels.  That is not reproduced. */
 int d2pc_fusion_node_geometry(const d2pc_fusion_node_config *cfg, d2pc_fusion_node_geometry_t *out);
 
 typedef struct d2pc_fusion_node d2pc_fusion_node;

@@ -1,8 +1,15 @@
 """ctypes binding of the CPU oracle (oracle/d2pc_oracle.c).
 
-TEST INFRASTRUCTURE ONLY -- PARITY UNPINNED (see d2pc_oracle.h).  Importable
-from tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg; the
-product package `disparity_to_point_cloud_amd` never imports it.
+TEST INFRASTRUCTURE ONLY (see d2pc_oracle.h).  Importable from tests/,
+__graft_entry__.smoke() and bench.py's cpu_baseline leg; the product package
+`disparity_to_point_cloud_amd` never imports it.
+
+PARITY: the depth-map-fusion half (fuse_pixel, fuse, crop_to_square, rotate_cw)
+is pinned to the reference's own compiled depth_map_fusion.cpp (oracle/ref.py,
+tests/test_reference_cpu.py), apart from the three OpenCV filters and
+medianBlur, which the reference only calls.  The reprojection half (reproject,
+median_u8, mono16_to_mono8, make_q) stays UNPINNED: its arithmetic sits inside
+OpenCV and PCL.
 """
 import ctypes
 import os
@@ -21,7 +28,8 @@ _lib = None
 
 
 def build(force: bool = False) -> str:
-    """Compile the C restatement with gcc (oracle/Makefile)."""
+    """Compile the C restatement with gcc (oracle/Makefile) and, where the reference's sources are on this machine,
+    the reference itself against oracle/ref_shim into oracle/_ref/ (oracle/ref.py)."""
     src = os.path.join(_HERE, "d2pc_oracle.c")
     stale = (not os.path.exists(_LIB_PATH)) or any(
         os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(_LIB_PATH)
@@ -30,6 +38,9 @@ def build(force: bool = False) -> str:
     if force or stale:
         subprocess.run(["make", "-C", _HERE, "-B"], check=True, capture_output=True)
     assert os.path.exists(_LIB_PATH), src
+    from . import ref
+
+    ref.build_ref(force)
     return _LIB_PATH
 
 
@@ -62,6 +73,8 @@ def lib():
         L.d2pc_oracle_max_threads.restype = ctypes.c_int
         L.d2pc_oracle_fuse_pixel.argtypes = [ctypes.c_int] * 7
         L.d2pc_oracle_fuse_pixel.restype = ctypes.c_int
+        L.d2pc_oracle_fuse_pixels.argtypes = [ctypes.c_int, ctypes.c_size_t] + [ctypes.c_void_p] * 7
+        L.d2pc_oracle_fuse_pixels.restype = None
         L.d2pc_oracle_fuse.argtypes = [
             ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int, ctypes.c_int, ctypes.c_int,
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
@@ -162,6 +175,19 @@ REFERENCE_CROP = (0, 40, 30, 10)  # left, right, top, bottom at cpp:130
 
 def fuse_pixel(rule, d1, d2, s1, s2, g1=0, g2=0) -> int:
     return lib().d2pc_oracle_fuse_pixel(rule, d1, d2, s1, s2, g1, g2)
+
+
+def fuse_pixels(rule, d1, d2, s1, s2, g1=None, g2=None) -> np.ndarray:
+    """fuse_pixel over flat uint8 arrays -> int16."""
+    arrs = [np.ascontiguousarray(a, dtype=np.uint8).ravel() for a in (d1, d2, s1, s2)]
+    n = arrs[0].size
+    assert all(a.size == n for a in arrs)
+    gs = [None if g is None else np.ascontiguousarray(g, dtype=np.uint8).ravel() for g in (g1, g2)]
+    assert all(g is None or g.size == n for g in gs)
+    out = np.empty(n, dtype=np.int16)
+    lib().d2pc_oracle_fuse_pixels(rule, n, *[a.ctypes.data for a in arrs],
+                                  *[None if g is None else g.ctypes.data for g in gs], out.ctypes.data)
+    return out
 
 
 def fuse(planes, rule=FUSE_GRAD_FILTER, crop=REFERENCE_CROP, want_combined=True):

@@ -6,12 +6,13 @@
  * build, load or call this code, and only as the checker / the timed CPU
  * baseline.  The product library (libd2pc.so) never links or dlopens it.
  *
- * PARITY UNPINNED.  The reference (PX4/disparity_to_point_cloud) ships no
- * tests and no golden data, and its arithmetic lives in un-vendored,
- * un-pinned third-party libraries (OpenCV calib3d/imgproc/core, cv_bridge,
- * PCL, pcl_conversions; only hint: ROS Indigo => OpenCV 2.4.x, PCL 1.7).
- * None of them can be built in this image, so this file restates their
- * published algorithms and is anchored on the reference's own call sites:
+ * PARITY UNPINNED FOR THE REPROJECTION HALF.  The reference
+ * (PX4/disparity_to_point_cloud) ships no tests and no golden data, and the
+ * point-cloud node's arithmetic lives in un-vendored, un-pinned third-party
+ * libraries (OpenCV calib3d/imgproc/core, cv_bridge, PCL, pcl_conversions;
+ * only hint: ROS Indigo => OpenCV 2.4.x, PCL 1.7).  None of them can be built
+ * in this image, so this file restates their published algorithms and is
+ * anchored on the reference's own call sites:
  *
  *   src/disparity_to_point_cloud.cpp:50     cv_bridge::toCvCopy(*msg,"mono8")
  *   src/disparity_to_point_cloud.cpp:55-57  cv::medianBlur(..., 11)
@@ -102,7 +103,14 @@ void d2pc_oracle_median_u8_fast(const uint8_t *src, size_t src_stride_bytes,
                                 uint8_t *dst, size_t dst_stride_bytes,
                                 int width, int height, int ksize);
 
-/* ---- depth-map fusion inner loop (d2pc_oracle_fusion.c) ---- */
+/* ---- depth-map fusion inner loop (d2pc_oracle_fusion.c) ----
+ * PINNED: src/depth_map_fusion.cpp keeps its arithmetic in its own text, so the
+ * reference itself is compiled (oracle/ref.py, oracle/ref_shim/) and
+ * tests/test_reference_cpu.py holds everything below equal to it: the nine
+ * rules over every input, cropToSquare / cropMat / rotateMat, the node's
+ * aliasing and publishing order.  Not pinned: cv::GaussianBlur, cv::Sobel,
+ * cv::threshold and cv::medianBlur, whose arithmetic stays this project's
+ * reading of OpenCV. */
 /* The nine candidate rules of src/depth_map_fusion.cpp:162-235, numbered in
  * source order; GRAD_FILTER is the one getFusedDistance calls (cpp:159). */
 enum {
@@ -119,6 +127,9 @@ enum {
 /* One pixel of cpp:150-160 (the int the rule returns, before the store to
  * unsigned char); -1 for an unknown rule. */
 int d2pc_oracle_fuse_pixel(int rule, int d1, int d2, int s1, int s2, int g1, int g2);
+/* The same for `count` pixels: out[i] = d2pc_oracle_fuse_pixel(rule, d1[i], ...); g1 / g2 may be null (0). */
+void d2pc_oracle_fuse_pixels(int rule, size_t count, const uint8_t *d1, const uint8_t *d2, const uint8_t *s1,
+                             const uint8_t *s2, const uint8_t *g1, const uint8_t *g2, int16_t *out);
 /* cpp:113-130: planes = {depth1, depth2, score1, score2, grad1, grad2}.
  * Returns 0, or <0 on bad arguments / allocation failure. */
 int d2pc_oracle_fuse(const uint8_t *const planes[6], const size_t pitch[6], int w, int h, int rule,

@@ -1,7 +1,8 @@
 /*
  * d2pc_oracle_fusion.c -- CPU restatement of the depth-map fusion inner loop
- * (SURVEY.md section 8(f) #4).  TEST INFRASTRUCTURE ONLY, PARITY UNPINNED --
- * see d2pc_oracle.h.  Anchors in the reference:
+ * (SURVEY.md section 8(f) #4).  TEST INFRASTRUCTURE ONLY.  Pinned to the compiled
+ * reference by tests/test_reference_cpu.py -- see d2pc_oracle.h.  Anchors in the
+ * reference:
  *
  *   src/depth_map_fusion.cpp:113-123  per-pixel fused distance + combined score
  *   src/depth_map_fusion.cpp:124      cv::medianBlur(image, image, 3)
@@ -56,6 +57,12 @@ int d2pc_oracle_fuse_pixel(int rule, int d1, int d2, int s1, int s2, int g1, int
     case D2PC_ORACLE_FUSE_GRAD_FILTER: return rule_grad_filter(d1, d2, s1, s2);
     default: return -1;
   }
+}
+
+void d2pc_oracle_fuse_pixels(int rule, size_t count, const uint8_t *d1, const uint8_t *d2, const uint8_t *s1,
+                             const uint8_t *s2, const uint8_t *g1, const uint8_t *g2, int16_t *out) {
+  for (size_t i = 0; i < count; i++)
+    out[i] = (int16_t)d2pc_oracle_fuse_pixel(rule, d1[i], d2[i], s1[i], s2[i], g1 ? g1[i] : 0, g2 ? g2[i] : 0);
 }
 
 /* cpp:113-130 for one set of n-by-n (here: w-by-h) planes.  `combined`

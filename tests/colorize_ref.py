@@ -94,6 +94,13 @@ class RefNode:
 
     def __init__(self, cols, rows, offset_x=0, offset_y=0, rule=oracle.FUSE_GRAD_FILTER, form=4):
         self.cols, self.rows, self.ox, self.oy, self.rule, self.form = cols, rows, offset_x, offset_y, rule, form
+        # The frame the reference fuses INTO is cropToSquare(image) of the incoming message (:106): arguments 0, side
+        # min(cols, rows) - |offset_y_| (:253).  The loop (:115-123) covers min(cols, rows) - max(|offset_x|, |offset_y|)
+        # of it.  Only with |offset_x| <= |offset_y| are the two the same square, as _fuse() below takes them to be;
+        # beyond that the compiled reference publishes a larger fused map (200 x 140 with 9 / -6: 94 x 94, not 91 x 91)
+        # with a margin of raw camera-2 pixels, which neither this model nor the product reproduces
+        # (tests/README_reference.md).
+        assert abs(offset_x) <= abs(offset_y), "|offset_x| > |offset_y|: refused by the product, not modelled here"
         self.sq1 = oracle.crop_to_square(cols, rows, offset_x, offset_y)
         self.sq2 = oracle.crop_to_square(rows, cols, -offset_x, -offset_y, offset_y)  # member offset_y_ (:253)
         assert self.sq1[2] == self.sq2[2]

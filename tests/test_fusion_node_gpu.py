@@ -74,7 +74,7 @@ def test_camera_2_negated_offsets_and_member_offset_y(ctx):
     assert node.sq1 == oracle.crop_to_square(752, 480, -7, 15)
     assert node.sq2 == oracle.crop_to_square(480, 752, 7, -15, 15)
     assert node.sq2 != oracle.crop_to_square(480, 752, -7, 15, 15)
-    _run(ctx, 200, 140, 9, -6, ["D2", "D1", "S2", "S1", "D2"], seed=3)
+    _run(ctx, 200, 140, 6, -9, ["D2", "D1", "S2", "S1", "D2"], seed=3)
 
 
 def test_fusion_withheld_until_the_fourth_plane(ctx):
@@ -108,7 +108,7 @@ def test_twenty_interleaved_callbacks(ctx):
     rng = np.random.default_rng(20)
     order = [["D1", "D2", "S1", "S2"][i] for i in rng.integers(0, 4, size=20)]
     assert len(set(order)) == 4
-    _run(ctx, 170, 130, 5, 3, order, seed=21)
+    _run(ctx, 170, 130, 3, 5, order, seed=21)
 
 
 def test_form_cv3_and_another_rule(ctx):

@@ -89,6 +89,9 @@ def test_geometry_refusals():
     assert status(cols=40, rows=40) == 3                     # the default crop leaves nothing of 40 x 40
     assert status(cols=60, rows=60, crop_top=25, crop_bottom=35) == 3
     assert status(cols=100, rows=100, offset_x=0, offset_y=20) == 0   # (the member offset_y is the argument here: the square fits)
+    # |offset_x| > |offset_y|: the reference fuses a smaller square than it publishes; refused
+    assert status(offset_x=5, offset_y=-4) == 3 and status(offset_x=-1, offset_y=0) == 3
+    assert status(offset_x=4, offset_y=-5) == 0 and status(offset_x=-5, offset_y=5) == 0 and status(offset_x=0, offset_y=-9) == 0
     assert status(cols=0) == 3 and status(rows=-1) == 3 and status(batch=0) == 3 and status(batch=70000) == 3
     assert status(crop_right=-1) == 3
     assert status(rule=9) == 1 and status(rule=-1) == 1 and status(score_form=5) == 1        # bad enums

@@ -93,7 +93,7 @@ def test_camera_2_negated_offsets_and_member_offset_y(ctx):
     assert s.sq2 == oracle.crop_to_square(480, 752, 7, -15, 15)
     assert s.sq2 != oracle.crop_to_square(480, 752, -7, 15, 15)
     s.close()
-    _run(ctx, 200, 140, 9, -6, ["D2", "D1", "S2", "S1", "D2"], seed=3)[0].close()
+    _run(ctx, 200, 140, 6, -9, ["D2", "D1", "S2", "S1", "D2"], seed=3)[0].close()
 
 
 def test_fusion_withheld_until_the_fourth_plane(ctx):
@@ -125,7 +125,7 @@ def test_twenty_interleaved_callbacks(ctx):
     rng = np.random.default_rng(20)
     order = [["D1", "D2", "S1", "S2"][i] for i in rng.integers(0, 4, size=20)]
     assert len(set(order)) == 4
-    _run(ctx, 170, 130, 5, 3, order, seed=21)[0].close()
+    _run(ctx, 170, 130, 3, 5, order, seed=21)[0].close()
 
 
 def test_form_cv3_and_another_rule(ctx):
@@ -301,13 +301,13 @@ def test_pitches_and_unaligned_bases(ctx, pad, shift):
 
 
 def test_batch_of_sixteen(ctx):
-    s = d2pc.FusionSession(ctx, 200, 150, 3, -2)
+    s = d2pc.FusionSession(ctx, 200, 150, 2, -3)
     n = s.n
     s.close()
     rng = np.random.default_rng(80)
     planes = [rng.integers(0, 256, size=(16, n, n)).astype(np.uint8) for _ in range(2)] + \
              [rng.integers(60, 140, size=(16, n, n)).astype(np.uint8) for _ in range(2)]
-    _fuse_planes(ctx, 200, 150, 3, -2, *planes, batch=16, pad=8, shift=1)
+    _fuse_planes(ctx, 200, 150, 2, -3, *planes, batch=16, pad=8, shift=1)
     # ... and a batch large enough for the tall tiles (2048 tiles of 64 x 64): 16 frames of n = 736
     s = d2pc.FusionSession(ctx, 740, 736, 0, 0)
     n = s.n

@@ -57,7 +57,7 @@ def test_host_entry_equals_the_model(ctx, single):
 
 
 def test_host_entry_batch(ctx):
-    cols, rows, ox, oy = 120, 150, 3, -2
+    cols, rows, ox, oy = 120, 150, 2, -3
     s = d2pc.FusionSession(ctx, cols, rows, ox, oy, batch=3)
     models = [ref.RefNode(cols, rows, ox, oy) for _ in range(3)]
     rng = np.random.default_rng(91)

@@ -19,20 +19,21 @@
 //                    the elevation table (ce_i, se_i) in LDS behind the azimuth table, gates on the Euclidean d2 and on the
 //                    band's two boundaries, counts the interior boundaries below the point in a second loop of the azimuth
 //                    loop's shape (one broadcast LDS read per boundary serves the lane's four records) and keys on d2.
+//                    Where a record falls (picks, gates, half turn, a step of either boundary count, the key's bits) is
+//                    d2pc_sectors_bin.hpp's, which the memory's kernel calls too; here are the loads, the two loops' skeletons
+//                    and the tables of cells.
 // k_sectors_finish   min / sum over the slabs, coalesced across cells (8 cells x 32 slices of the slabs per block, a
 //                    tree through LDS over the slices), then the outputs the caller asked for.
 // Keys are integers and counts are sums of integers: the result is the same bytes whatever order lanes, waves and
 // blocks arrive in.  Every float expression of the specification is rounded once: contraction is off in this file.
 #include <hip/hip_runtime.h>
 
-#include "d2pc_sectors_plan.hpp"
-
+#include "d2pc_sectors_bin.hpp"
 
 namespace d2pc {
 namespace sectors {
 namespace {
 
-constexpr uint32_t kNone = 0xFFFFFFFFu;   // a lane without a participating point
 [[maybe_unused]] constexpr int kWaveRounds = 2;   // elected cells per wave and record slot ...
 [[maybe_unused]] constexpr int kWaveRoundsMaxCells = 72;   // ... for grids up to this many cells; none beyond
 constexpr int kFinishCells = 8, kFinishSlices = 32;
@@ -49,11 +50,8 @@ struct Args {   // Launch without its host-only members
   uint16_t *distance_cm;
   uint64_t stride, shares;
   uint32_t shares_per_cloud, cloud_points, n_clouds, step16;
-  int n_sectors, n_layers, n_cells, half, blocks, rounds;
-  float rmin2, rmax2, u_min, u_max, inv_h;
-  int axis[3];
-  uint32_t flip[3];
-  uint32_t min_count, no_obstacle_cm;
+  int blocks, rounds;
+  GridArgs grid;
 };
 
 // the minimum over the wave's 64 lanes, in every lane; all 64 lanes are active at every call (the callers' control
@@ -69,10 +67,6 @@ __device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
   D2PC_DPP_MIN(0x143, 0xc);
 #undef D2PC_DPP_MIN
   return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
-
-__device__ __forceinline__ float pick(const uint4 &p, int axis, uint32_t flip) {
-  return __uint_as_float((axis == 0 ? p.x : axis == 1 ? p.y : p.z) ^ flip);
 }
 
 // one record slot of the wave into the block's table
@@ -105,15 +99,15 @@ template <int kKind>
 __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
 #pragma clang fp contract(off)
   constexpr bool kElevation = kKind == D2PC_SECTORS_LAYERS_ELEVATION;
+  const GridArgs g = a.grid;
   extern __shared__ __align__(16) unsigned char lds[];
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(lds);
-  uint32_t *cnts = reinterpret_cast<uint32_t *>(keys + a.n_cells);
-  float2 *tab = reinterpret_cast<float2 *>(cnts + a.n_cells);   // (n_cells is even: 8-byte aligned)
-  [[maybe_unused]] const float2 *etab = tab + a.half;           // n_layers + 1 x (ce, se), behind the azimuth table
+  uint32_t *cnts = reinterpret_cast<uint32_t *>(keys + g.n_cells);
+  float2 *tab = reinterpret_cast<float2 *>(cnts + g.n_cells);   // (n_cells is even: 8-byte aligned)
   const uint32_t tid = threadIdx.x;
-  for (int i = int(tid); i < a.n_cells; i += kThreads) keys[i] = ~0ull, cnts[i] = 0u;
-  // (the session's device table holds the elevation table behind the azimuth table, as the LDS does)
-  for (int j = int(tid); j < a.half + (kElevation ? a.n_layers + 1 : 0); j += kThreads) tab[j] = a.table[j];
+  for (int i = int(tid); i < g.n_cells; i += kThreads) keys[i] = ~0ull, cnts[i] = 0u;
+  // (the session's device table holds the elevation table, n_layers + 1 x (ce, se), behind the azimuth table, as the LDS does)
+  for (int j = int(tid); j < g.half + (kElevation ? g.n_layers + 1 : 0); j += kThreads) tab[j] = a.table[j];
   __syncthreads();
 
   for (uint64_t share = blockIdx.x; share < a.shares; share += uint64_t(a.blocks)) {
@@ -141,74 +135,34 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
       if (have[k]) rec[k] = a.points[(first + i) * a.step16];
       asm volatile("" ::"v"(rec[k].w));   // keeps the load a whole 16-byte one (w is not used: it would shrink to 12)
     }
-    float f[kPerLane], l[kPerLane];
-    uint32_t cell[kPerLane], r2_bits[kPerLane], sector[kPerLane];
-    [[maybe_unused]] float up[kPerLane], hz[kPerLane];   // elevation: u and the horizontal range h = sqrtf(r2)
-    const float2 t0 = tab[0];
-    [[maybe_unused]] float2 lo, hi;   // elevation: the band's two boundaries
-    if constexpr (kElevation) lo = etab[0], hi = etab[a.n_layers];
+    // where the lane's four records fall (d2pc_sectors_bin.hpp)
+    float f[kPerLane], l[kPerLane], up[kPerLane], hz[kPerLane];
+    uint32_t cell[kPerLane], key_bits[kPerLane], sector[kPerLane], layer[kPerLane] = {};
+    const float2 t0 = tab[0], lo = tab[kElevation ? g.half : 0], hi = tab[kElevation ? g.half + g.n_layers : 0];
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k) {
-      const uint4 p = rec[k];
-      const bool finite = (p.x & 0x7F800000u) != 0x7F800000u && (p.y & 0x7F800000u) != 0x7F800000u && (p.z & 0x7F800000u) != 0x7F800000u;
-      const float ff = pick(p, a.axis[0], a.flip[0]), ll = pick(p, a.axis[1], a.flip[1]);
-      const float u = pick(p, a.axis[2], a.flip[2]);
-      const float r2 = ff * ff + ll * ll;
-      bool in;
-      uint32_t layer = 0;
-      float key = r2;
-      if constexpr (kElevation) {
-        // the band's two boundaries are gates; `!(t >= 0)` and `t >= 0` as written: a NaN t (0 * inf) takes no part
-        const float h = __builtin_sqrtf(r2);   // (the correctly rounded one: the file's flags)
-        key = r2 + u * u;
-        const float t_lo = lo.x * u - lo.y * h, t_hi = hi.x * u - hi.y * h;
-        in = have[k] && finite && r2 > 0.0f && key >= a.rmin2 && key <= a.rmax2 && t_lo >= 0.0f && !(t_hi >= 0.0f);
-        up[k] = u, hz[k] = h;
-      } else {
-        in = have[k] && finite && r2 > 0.0f && r2 >= a.rmin2 && r2 <= a.rmax2 && u >= a.u_min && u < a.u_max;
-        if (a.n_layers > 1) {
-          const float slab = floorf((u - a.u_min) * a.inv_h);
-          layer = slab >= float(a.n_layers - 1) ? uint32_t(a.n_layers - 1) : uint32_t(int(slab));   // (in: slab >= 0)
-        }
-      }
-      const float cross0 = t0.x * ll - t0.y * ff, dot0 = t0.x * ff + t0.y * ll;
-      // the half turn as a sign-bit mask, without a branch: hipcc of ROCm 7 structurised `if (A || (B && C)) negate` so
-      // that the lanes of B && C kept f and l un-negated (tests/test_sectors_gpu.py: l = +-0 with f < 0)
-      const uint32_t turn = (uint32_t(cross0 < 0.0f) | (uint32_t(cross0 == 0.0f) & uint32_t(dot0 < 0.0f))) << 31;
-      f[k] = __uint_as_float(__float_as_uint(ff) ^ turn), l[k] = __uint_as_float(__float_as_uint(ll) ^ turn);
-      sector[k] = turn ? uint32_t(a.half) : 0u;
-      cell[k] = in ? layer * uint32_t(a.n_sectors) : kNone;
-      r2_bits[k] = __float_as_uint(key);
+      const Binned b = bin_record<kElevation, const uint4 &>(g, t0, lo, hi, rec[k], have[k]);
+      f[k] = b.f, l[k] = b.l, up[k] = b.up, hz[k] = b.hz, cell[k] = b.cell, key_bits[k] = b.key_bits, sector[k] = b.sector;
     }
-    // the count of the boundaries behind the point: one LDS read of (c_j, s_j) serves the lane's four records, and
-    // every lane reads the same address (a broadcast: no bank conflict)
-    for (int j = 1; j < a.half; ++j) {
+    for (int j = 1; j < g.half; ++j) {
       const float2 t = tab[j];
 #pragma unroll
-      for (int k = 0; k < kPerLane; ++k) sector[k] += (t.x * l[k] - t.y * f[k]) >= 0.0f ? 1u : 0u;
+      for (int k = 0; k < kPerLane; ++k) sector[k] += behind(t, l[k], f[k]);
     }
-    if constexpr (kElevation) {
-      // the layer: the interior boundaries at or below the point, counted like the sectors (a compare folded into an add)
-      uint32_t layer[kPerLane] = {};
-      for (int i = 1; i < a.n_layers; ++i) {
-        const float2 t = etab[i];
+    for (int i = 1; kElevation && i < g.n_layers; ++i) {
+      const float2 t = tab[g.half + i];
 #pragma unroll
-        for (int k = 0; k < kPerLane; ++k) layer[k] += (t.x * up[k] - t.y * hz[k]) >= 0.0f ? 1u : 0u;
-      }
-#pragma unroll
-      for (int k = 0; k < kPerLane; ++k) sector[k] += layer[k] * uint32_t(a.n_sectors);   // (cell[k] is 0 or kNone here)
+      for (int k = 0; k < kPerLane; ++k) layer[k] += behind(t, up[k], hz[k]);
     }
 #pragma unroll
-    for (int k = 0; k < kPerLane; ++k) {
-      const uint32_t c = cell[k] == kNone ? kNone : cell[k] + sector[k];
-      merge(keys, cnts, a.rounds, c, r2_bits[k], uint32_t(first) + i0 + uint32_t(k * kThreads) + tid);
-    }
+    for (int k = 0; k < kPerLane; ++k)
+      merge(keys, cnts, a.rounds, cell_of(g, cell[k], sector[k], layer[k]), key_bits[k], uint32_t(first) + i0 + uint32_t(k * kThreads) + tid);
   }
 
   __syncthreads();
-  unsigned long long *slab_k = reinterpret_cast<unsigned long long *>(a.slab_keys) + size_t(blockIdx.x) * size_t(a.n_cells);
-  uint32_t *slab_c = a.slab_counts + size_t(blockIdx.x) * size_t(a.n_cells);
-  for (int i = int(tid); i < a.n_cells; i += kThreads) slab_k[i] = keys[i], slab_c[i] = cnts[i];
+  unsigned long long *slab_k = reinterpret_cast<unsigned long long *>(a.slab_keys) + size_t(blockIdx.x) * size_t(g.n_cells);
+  uint32_t *slab_c = a.slab_counts + size_t(blockIdx.x) * size_t(g.n_cells);
+  for (int i = int(tid); i < g.n_cells; i += kThreads) slab_k[i] = keys[i], slab_c[i] = cnts[i];
 }
 
 __global__ __launch_bounds__(kThreads) void k_sectors_finish(const Args a) {
@@ -217,13 +171,14 @@ __global__ __launch_bounds__(kThreads) void k_sectors_finish(const Args a) {
   __shared__ uint32_t sc[kThreads];
   const int tid = int(threadIdx.x), slice = tid / kFinishCells;
   const int cell = int(blockIdx.x) * kFinishCells + tid % kFinishCells;
+  const int n_cells = a.grid.n_cells;
   unsigned long long key = ~0ull;
   uint32_t cnt = 0;
-  if (cell < a.n_cells) {
+  if (cell < n_cells) {
     const unsigned long long *slab_k = reinterpret_cast<const unsigned long long *>(a.slab_keys);
 #pragma unroll 8
     for (int b = slice; b < a.blocks; b += kFinishSlices) {
-      const size_t at = size_t(b) * size_t(a.n_cells) + size_t(cell);
+      const size_t at = size_t(b) * size_t(n_cells) + size_t(cell);
       const unsigned long long k = slab_k[at];
       key = k < key ? k : key;
       cnt += a.slab_counts[at];
@@ -239,25 +194,22 @@ __global__ __launch_bounds__(kThreads) void k_sectors_finish(const Args a) {
       sk[tid] = key, sc[tid] = cnt;
     }
   }
-  if (slice != 0 || cell >= a.n_cells) return;
-  const bool seen = cnt >= a.min_count;   // (min_count >= 1: an empty cell is never seen)
-  const float range = seen ? __builtin_sqrtf(__uint_as_float(uint32_t(key >> 32))) : __uint_as_float(0x7F800000u);
+  if (slice != 0 || cell >= n_cells) return;
+  const bool seen = cnt >= a.grid.min_count;   // (min_count >= 1: an empty cell is never seen)
+  const float range = seen ? range_of_key(key) : __uint_as_float(0x7F800000u);
   if (a.range) a.range[cell] = range;
   if (a.count) a.count[cell] = cnt;
   if (a.nearest) a.nearest[cell] = uint32_t(key);   // (the empty key's low word is the empty mark)
-  if (a.distance_cm) {
-    const float cm = range * 100.0f;
-    a.distance_cm[cell] = uint16_t(!seen ? a.no_obstacle_cm : cm >= 65534.0f ? 65534u : uint32_t(cm));
-  }
+  if (a.distance_cm) a.distance_cm[cell] = distance_cm_of(a.grid, range, !seen);
 }
 
-}  // namespace
-
-// the instantiation a session of plan `p` launches
+// the instantiation a session of plan `p` launches: the one place that turns a layer kind into a kernel
 const void *reduce_kernel(const Plan &p) {
   return p.layer_kind == D2PC_SECTORS_LAYERS_ELEVATION ? reinterpret_cast<const void *>(&k_sectors_reduce<D2PC_SECTORS_LAYERS_ELEVATION>)
                                                        : reinterpret_cast<const void *>(&k_sectors_reduce<D2PC_SECTORS_LAYERS_HEIGHT>);
 }
+
+}  // namespace
 
 int prepare_sectors_kernels(const Plan &p) {
   // beyond 64 KB of dynamic LDS the runtime wants to be told (360 x 16 cells need 70,560 bytes, 90 x 64 elevation cells
@@ -275,20 +227,15 @@ int launch_sectors(const Launch &in) {
   a.stride = in.stride, a.shares = in.shares;
   a.shares_per_cloud = in.shares_per_cloud, a.cloud_points = in.cloud_points, a.n_clouds = in.n_clouds, a.step16 = in.step16;
   const Plan &p = in.plan;
-  a.n_sectors = p.n_sectors, a.n_layers = p.n_layers, a.n_cells = p.n_cells, a.half = p.half, a.blocks = in.blocks;
+  a.grid = grid_args(p), a.blocks = in.blocks;
 #ifdef D2PC_SECTORS_FORCE_ROUNDS
   a.rounds = D2PC_SECTORS_FORCE_ROUNDS;
 #else
   a.rounds = p.n_cells <= kWaveRoundsMaxCells ? kWaveRounds : 0;
 #endif
-  a.rmin2 = p.rmin2, a.rmax2 = p.rmax2, a.u_min = p.u_min, a.u_max = p.u_max, a.inv_h = p.inv_h;
-  for (int i = 0; i < 3; ++i) a.axis[i] = p.axis[i], a.flip[i] = p.flip[i];
-  a.min_count = p.min_count, a.no_obstacle_cm = p.no_obstacle_cm;
   hipStream_t s = static_cast<hipStream_t>(in.stream);
-  if (p.layer_kind == D2PC_SECTORS_LAYERS_ELEVATION)
-    hipLaunchKernelGGL(k_sectors_reduce<D2PC_SECTORS_LAYERS_ELEVATION>, dim3(unsigned(in.blocks)), dim3(kThreads), p.lds_bytes, s, a);
-  else
-    hipLaunchKernelGGL(k_sectors_reduce<D2PC_SECTORS_LAYERS_HEIGHT>, dim3(unsigned(in.blocks)), dim3(kThreads), p.lds_bytes, s, a);
+  void *args[] = {&a};
+  (void)hipLaunchKernel(reduce_kernel(p), dim3(unsigned(in.blocks)), dim3(kThreads), args, p.lds_bytes, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return int(e);
   hipLaunchKernelGGL(k_sectors_finish, dim3(unsigned((p.n_cells + kFinishCells - 1) / kFinishCells)), dim3(kThreads), 0, s, a);

@@ -2,13 +2,9 @@
 // memory; an elevation session's second table behind it) and the one asynchronous call.  Everything that needs no device -- the refusals, rmin2 / rmax2 / inv_h, the
 // table's values -- is d2pc_sectors_plan.hpp's; this file adds the device.  libd2pc_sectors.so links the HIP runtime
 // only: nothing of d2pc_ctx is needed to read records from device memory.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
 #include <new>
-#include <vector>
 
-#include "d2pc_sectors_plan.hpp"
+#include "d2pc_sectors_session.hpp"
 
 using namespace d2pc::sectors;
 
@@ -21,31 +17,6 @@ struct d2pc_sectors {
   uint32_t *d_slab_counts = nullptr;
   char err[256] = "";
 };
-
-namespace {
-
-struct DeviceGuard {   // selects the session's device for a scope (as the contexts of libd2pc.so do)
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-int fail(d2pc_sectors *s, int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(s->err, sizeof s->err, fmt, ap);
-  va_end(ap);
-  return status;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -110,11 +81,7 @@ int d2pc_sectors_create(const d2pc_sectors_config *cfg, d2pc_sectors **out) {
   Plan p;
   const int st = make_plan(cfg, &p);
   if (st != D2PC_OK) return st;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || cfg->device_id < 0 || cfg->device_id >= n_dev) {
-    (void)hipGetLastError();
-    return D2PC_ERR_NO_DEVICE;
-  }
+  if (!device_exists(cfg->device_id)) return D2PC_ERR_NO_DEVICE;
   DeviceGuard guard(cfg->device_id);
   if (!guard.ok) return D2PC_ERR_NO_DEVICE;
   int cus = 0;
@@ -123,16 +90,10 @@ int d2pc_sectors_create(const d2pc_sectors_config *cfg, d2pc_sectors **out) {
   if (!s) return D2PC_ERR_OUT_OF_MEMORY;
   s->cfg = *cfg, s->plan = p, s->device = cfg->device_id;
   s->blocks = p.blocks_per_cu * cus;
-  const size_t pairs = size_t(p.half) + size_t(p.elev);
-  std::vector<float> table(pairs * 2), cs(pairs), sn(pairs);
-  fill_table(*cfg, cs.data(), sn.data());
-  if (p.elev) fill_elevation_table(*cfg, cs.data() + p.half, sn.data() + p.half);
-  for (size_t j = 0; j < pairs; ++j) table[2 * j] = cs[j], table[2 * j + 1] = sn[j];
   const size_t cells = size_t(s->blocks) * size_t(p.n_cells);
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->d_table), table.size() * sizeof(float));
+  hipError_t e = upload_table(*cfg, p, &s->d_table);
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_slab_keys), cells * sizeof(uint64_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&s->d_slab_counts), cells * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(s->d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipError_t(prepare_sectors_kernels(p));
   if (e != hipSuccess) {
     (void)d2pc_sectors_destroy(s);
@@ -161,7 +122,7 @@ int d2pc_sectors_process_device(d2pc_sectors *s, const d2pc_sectors_desc *d, voi
   const int st = check_desc(s->plan, d, s->err, sizeof s->err);
   if (st != D2PC_OK) return st;
   DeviceGuard guard(s->device);
-  if (!guard.ok) return fail(s, D2PC_ERR_NO_DEVICE, "cannot select device %d", s->device);
+  if (!guard.ok) return fail(s->err, D2PC_ERR_NO_DEVICE, "cannot select device %d", s->device);
   Launch a;
   a.plan = s->plan;
   a.points = d->points, a.counts = d->counts, a.table = s->d_table;
@@ -174,7 +135,7 @@ int d2pc_sectors_process_device(d2pc_sectors *s, const d2pc_sectors_desc *d, voi
   a.blocks = s->blocks;
   a.stream = stream;   // NULL = HIP's default stream
   const hipError_t e = hipError_t(launch_sectors(a));
-  if (e != hipSuccess) return fail(s, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(s->err, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
   return D2PC_OK;
 }
 

@@ -1,13 +1,11 @@
 // d2pc_sectors_memory_capi.hip -- include/d2pc_sectors.h: the memory session (two record buffers, a parity word and the
 // grid's tables in device memory) and its asynchronous calls.  Everything that needs no device -- the refusals, the
 // position bound, the coverage -- is d2pc_sectors_memory_plan.hpp's; this file adds the device.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
 #include <new>
 #include <vector>
 
 #include "d2pc_sectors_memory_plan.hpp"
+#include "d2pc_sectors_session.hpp"
 
 using namespace d2pc::sectors;
 
@@ -20,31 +18,6 @@ struct d2pc_sectors_memory {
   char err[256] = "";
 };
 
-namespace {
-
-struct DeviceGuard {   // selects the session's device for a scope (as d2pc_sectors_capi.hip's does)
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-int fail(d2pc_sectors_memory *m, int status, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(m->err, sizeof m->err, fmt, ap);
-  va_end(ap);
-  return status;
-}
-
-}  // namespace
-
 extern "C" {
 
 int d2pc_sectors_memory_create(const d2pc_sectors_config *grid, const d2pc_sectors_memory_config *mcfg, d2pc_sectors_memory **out) {
@@ -53,28 +26,19 @@ int d2pc_sectors_memory_create(const d2pc_sectors_config *grid, const d2pc_secto
   MemoryPlan p;
   const int st = make_memory_plan(grid, mcfg, &p);
   if (st != D2PC_OK) return st;
-  int n_dev = 0;
-  if (hipGetDeviceCount(&n_dev) != hipSuccess || grid->device_id < 0 || grid->device_id >= n_dev) {
-    (void)hipGetLastError();
-    return D2PC_ERR_NO_DEVICE;
-  }
+  if (!device_exists(grid->device_id)) return D2PC_ERR_NO_DEVICE;
   DeviceGuard guard(grid->device_id);
   if (!guard.ok) return D2PC_ERR_NO_DEVICE;
   d2pc_sectors_memory *m = new (std::nothrow) d2pc_sectors_memory();
   if (!m) return D2PC_ERR_OUT_OF_MEMORY;
   m->plan = p, m->device = grid->device_id;
-  const size_t pairs = size_t(p.grid.half) + size_t(p.grid.elev), n = size_t(p.grid.n_cells);
-  std::vector<float> table(pairs * 2), cs(pairs), sn(pairs);
-  fill_table(*grid, cs.data(), sn.data());
-  if (p.grid.elev) fill_elevation_table(*grid, cs.data() + p.grid.half, sn.data() + p.grid.half);
-  for (size_t j = 0; j < pairs; ++j) table[2 * j] = cs[j], table[2 * j + 1] = sn[j];
+  const size_t n = size_t(p.grid.n_cells);
   std::vector<uint32_t> empty(2 * n * 4, 0u);
   for (size_t i = 0; i < 2 * n; ++i) empty[4 * i + 3] = kEmptyAge;
   const uint32_t zero = 0;
-  hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->d_table), table.size() * sizeof(float));
+  hipError_t e = upload_table(*grid, p.grid, &m->d_table);
   if (e == hipSuccess) e = hipMalloc(&m->d_buffers, empty.size() * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->d_parity), sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(m->d_table, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->d_buffers, empty.data(), empty.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(m->d_parity, &zero, sizeof zero, hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -117,7 +81,7 @@ int d2pc_sectors_memory_update_device(d2pc_sectors_memory *m, const d2pc_sectors
   const int st = check_memory_desc(m->plan, d, m->err, sizeof m->err);
   if (st != D2PC_OK) return st;
   DeviceGuard guard(m->device);
-  if (!guard.ok) return fail(m, D2PC_ERR_NO_DEVICE, "cannot select device %d", m->device);
+  if (!guard.ok) return fail(m->err, D2PC_ERR_NO_DEVICE, "cannot select device %d", m->device);
   MemoryLaunch a;
   a.plan = m->plan;
   a.points = d->points, a.count = d->count, a.nearest = d->nearest, a.step = d->step, a.covered = d->covered;
@@ -126,16 +90,16 @@ int d2pc_sectors_memory_update_device(d2pc_sectors_memory *m, const d2pc_sectors
   a.bound = uint32_t(position_bound(*d)), a.step16 = uint32_t(d->point_step / 16);   // (the bound is 0xFFFFFFFF at the most)
   a.stream = stream;   // NULL = HIP's default stream
   const hipError_t e = hipError_t(launch_memory_update(a));
-  if (e != hipSuccess) return fail(m, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(m->err, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
   return D2PC_OK;
 }
 
 int d2pc_sectors_memory_reset_device(d2pc_sectors_memory *m, void *stream) {
   if (!m) return D2PC_ERR_INVALID_ARG;
   DeviceGuard guard(m->device);
-  if (!guard.ok) return fail(m, D2PC_ERR_NO_DEVICE, "cannot select device %d", m->device);
+  if (!guard.ok) return fail(m->err, D2PC_ERR_NO_DEVICE, "cannot select device %d", m->device);
   const hipError_t e = hipError_t(launch_memory_reset(m->d_buffers, m->plan.grid.n_cells, stream));
-  if (e != hipSuccess) return fail(m, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(m->err, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
   return D2PC_OK;
 }
 

@@ -1,7 +1,8 @@
 // d2pc_sectors_memory_plan.hpp -- the host side of the memory session of include/d2pc_sectors.h that needs no device:
-// what a memory configuration and a memory descriptor are refused for, the position bound, the LDS of the one block and
-// the coverage of the cells by the cameras' fields of view.  The grid's own refusals, constants and tables are
-// d2pc_sectors_plan.hpp's (make_plan, fill_table, fill_elevation_table).  Host code only and no HIP: plain g++ compiles
+// what a memory configuration and a memory descriptor are refused for, the LDS of the one block and the coverage of the
+// cells by the cameras' fields of view.  The grid's own refusals, constants and tables, the refusals of a descriptor's
+// cloud part and the position bound are d2pc_sectors_plan.hpp's (make_plan, fill_table, fill_elevation_table,
+// check_cloud_given / _sizes, position_bound).  Host code only and no HIP: plain g++ compiles
 // it (tests/test_sectors_memory_cpu.py, tests/cpp/sectors_memory_plan_main.cpp).
 #pragma once
 #include "d2pc_sectors_plan.hpp"
@@ -20,9 +21,6 @@ struct MemoryPlan {
   size_t lds_bytes;          // the carry keys (8 bytes a cell), then the azimuth and the elevation table
 };
 
-#define D2PC_SECTORS_REFUSE(st, ...) \
-  do { if (msg) snprintf(msg, msg_len, __VA_ARGS__); return st; } while (0)
-
 // D2PC_OK and *p filled, or the refusal: the grid's, as make_plan makes them, then the memory's own
 inline int make_memory_plan(const d2pc_sectors_config *grid, const d2pc_sectors_memory_config *m, MemoryPlan *p, char *msg = nullptr,
                             size_t msg_len = 0) {
@@ -35,35 +33,19 @@ inline int make_memory_plan(const d2pc_sectors_config *grid, const d2pc_sectors_
   return D2PC_OK;
 }
 
-// (n_clouds - 1) * stride + cloud_points of a checked descriptor: positions below it are records of `points`
-inline uint64_t position_bound(const d2pc_sectors_memory_desc &d) {
-  const uint64_t stride = d.n_clouds > 1 ? uint64_t(d.points_frame_stride_points) : 0;
-  return uint64_t(d.n_clouds - 1) * stride + uint64_t(d.cloud_points);
-}
-
 // what d2pc_sectors_memory_update_device refuses of a descriptor, for a session of plan `p`
 inline int check_memory_desc(const MemoryPlan &p, const d2pc_sectors_memory_desc *d, char *msg = nullptr, size_t msg_len = 0) {
   if (!d || d->struct_size != sizeof(d2pc_sectors_memory_desc)) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "bad d2pc_sectors_memory_desc");
-  if (d->point_step != 16 && d->point_step != 32) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "point_step of %d: 16 or 32", d->point_step);
-  if (d->n_clouds < 1 || d->n_clouds > 65535) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "n_clouds of %d: 1 .. 65,535", d->n_clouds);
-  if (!d->points) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "points is null");
+  if (const int st = check_cloud_given(*d, msg, msg_len)) return st;
   if (!d->count || !d->nearest) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "count or nearest is null");
   if (!d->step) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "step is null");
   if (!d->range && !d->distance_cm && !d->age && !d->records) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "no output is given");
-  auto misaligned = [](const void *q, size_t to) { return reinterpret_cast<uintptr_t>(q) % to != 0; };
   if (misaligned(d->points, 16)) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "points must be 16-byte aligned");
   if (misaligned(d->records, 16)) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "records must be 16-byte aligned");
   if (misaligned(d->count, 4) || misaligned(d->nearest, 4) || misaligned(d->step, 4) || misaligned(d->range, 4) ||
       misaligned(d->age, 4) || misaligned(d->distance_cm, 2))
     D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "count, nearest, step or an output is not aligned to its type");
-  const uint64_t cp = d->cloud_points;
-  if (cp == 0 || cp >= (uint64_t(1) << 32)) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "cloud_points of %zu: 1 .. 2^32 - 1", d->cloud_points);
-  const uint64_t stride = d->n_clouds > 1 ? uint64_t(d->points_frame_stride_points) : 0;
-  if (d->n_clouds > 1 && stride < cp) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the frame stride is smaller than cloud_points (%zu)", d->cloud_points);
-  // (n_clouds - 1) * stride + cloud_points - 1 <= 0xFFFFFFFE, formed so that nothing wraps
-  const uint64_t room = 0xFFFFFFFFull - cp;
-  if (d->n_clouds > 1 && stride > room / uint64_t(d->n_clouds - 1))
-    D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the position of the last record does not fit below 0xFFFFFFFF");
+  if (const int st = check_cloud_sizes(*d, msg, msg_len)) return st;
   const size_t n = size_t(p.grid.n_cells);
   const void *ins[5] = {d->points, d->count, d->nearest, d->step, d->covered};
   const size_t in_bytes[5] = {size_t(position_bound(*d) * uint64_t(d->point_step)), n * 4u, n * 4u, sizeof(d2pc_sectors_memory_step), n};
@@ -77,8 +59,6 @@ inline int check_memory_desc(const MemoryPlan &p, const d2pc_sectors_memory_desc
   }
   return D2PC_OK;
 }
-
-#undef D2PC_SECTORS_REFUSE
 
 // covered[cell] = 1 where the cell's centre direction lies inside some field of view, all in double (d2pc_sectors.h)
 inline void fill_coverage(const d2pc_sectors_config &c, const d2pc_sectors_fov *fovs, int n_fovs, uint8_t *covered) {

@@ -35,6 +35,7 @@ struct Plan {                // what the kernels get of a configuration
   int blocks_per_cu;
 };
 
+// (every refusal of this header and of d2pc_sectors_memory_plan.hpp: the status, and the reason in msg when given)
 #define D2PC_SECTORS_REFUSE(st, ...) \
   do { if (msg) snprintf(msg, msg_len, __VA_ARGS__); return st; } while (0)
 
@@ -132,27 +133,48 @@ inline bool hulls_meet(const void *a, size_t a_bytes, const void *b, size_t b_by
   return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
 }
 
+inline bool misaligned(const void *q, size_t to) { return reinterpret_cast<uintptr_t>(q) % to != 0; }
+
+// The cloud part of a descriptor of either kind (the sectors' or the memory's), in the two runs its refusals come in: a
+// descriptor's own null and alignment refusals, and the alignment of `points` between those, lie between the runs
+template <class Desc>
+inline int check_cloud_given(const Desc &d, char *msg, size_t msg_len) {
+  if (d.point_step != 16 && d.point_step != 32) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "point_step of %d: 16 or 32", d.point_step);
+  if (d.n_clouds < 1 || d.n_clouds > 65535) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "n_clouds of %d: 1 .. 65,535", d.n_clouds);
+  if (!d.points) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "points is null");
+  return D2PC_OK;
+}
+template <class Desc>
+inline int check_cloud_sizes(const Desc &d, char *msg, size_t msg_len) {
+  const uint64_t cp = d.cloud_points;
+  if (cp == 0 || cp >= (uint64_t(1) << 32)) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "cloud_points of %zu: 1 .. 2^32 - 1", d.cloud_points);
+  const uint64_t stride = d.n_clouds > 1 ? uint64_t(d.points_frame_stride_points) : 0;
+  if (d.n_clouds > 1 && stride < cp) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the frame stride is smaller than cloud_points (%zu)", d.cloud_points);
+  // (n_clouds - 1) * stride + cloud_points - 1 <= 0xFFFFFFFE, formed so that nothing wraps
+  const uint64_t room = 0xFFFFFFFFull - cp;
+  if (d.n_clouds > 1 && stride > room / uint64_t(d.n_clouds - 1))
+    D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the position of the last record does not fit below 0xFFFFFFFF");
+  return D2PC_OK;
+}
+
+// (n_clouds - 1) * stride + cloud_points of a checked descriptor of either kind: positions below it are records of `points`
+template <class Desc>
+inline uint64_t position_bound(const Desc &d) {
+  const uint64_t stride = d.n_clouds > 1 ? uint64_t(d.points_frame_stride_points) : 0;
+  return uint64_t(d.n_clouds - 1) * stride + uint64_t(d.cloud_points);
+}
+
 // what d2pc_sectors_process_device refuses of a descriptor, for a session of plan `p`
 inline int check_desc(const Plan &p, const d2pc_sectors_desc *d, char *msg = nullptr, size_t msg_len = 0) {
   if (!d || d->struct_size != sizeof(d2pc_sectors_desc)) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "bad d2pc_sectors_desc");
-  if (d->point_step != 16 && d->point_step != 32) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "point_step of %d: 16 or 32", d->point_step);
-  if (d->n_clouds < 1 || d->n_clouds > 65535) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "n_clouds of %d: 1 .. 65,535", d->n_clouds);
-  if (!d->points) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "points is null");
+  if (const int st = check_cloud_given(*d, msg, msg_len)) return st;
   if (!d->range && !d->count && !d->nearest && !d->distance_cm) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "no output is given");
-  auto misaligned = [](const void *q, size_t to) { return reinterpret_cast<uintptr_t>(q) % to != 0; };
   if (misaligned(d->points, 16)) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "points must be 16-byte aligned");
   if (misaligned(d->counts, 4) || misaligned(d->range, 4) || misaligned(d->count, 4) || misaligned(d->nearest, 4) ||
       misaligned(d->distance_cm, 2))
     D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "counts or an output is not aligned to its type");
-  const uint64_t cp = d->cloud_points;
-  if (cp == 0 || cp >= (uint64_t(1) << 32)) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "cloud_points of %zu: 1 .. 2^32 - 1", d->cloud_points);
-  const uint64_t stride = d->n_clouds > 1 ? uint64_t(d->points_frame_stride_points) : 0;
-  if (d->n_clouds > 1 && stride < cp) D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the frame stride is smaller than cloud_points (%zu)", d->cloud_points);
-  // (n_clouds - 1) * stride + cloud_points - 1 <= 0xFFFFFFFE, formed so that nothing wraps
-  const uint64_t room = 0xFFFFFFFFull - cp;
-  if (d->n_clouds > 1 && stride > room / uint64_t(d->n_clouds - 1))
-    D2PC_SECTORS_REFUSE(D2PC_ERR_BAD_SIZE, "the position of the last record does not fit below 0xFFFFFFFF");
-  const size_t in_bytes = size_t((uint64_t(d->n_clouds - 1) * stride + cp) * uint64_t(d->point_step));
+  if (const int st = check_cloud_sizes(*d, msg, msg_len)) return st;
+  const size_t in_bytes = size_t(position_bound(*d) * uint64_t(d->point_step));
   const size_t cnt_bytes = d->counts ? size_t(d->n_clouds) * 4u : 0;
   const size_t n = size_t(p.n_cells);
   const void *outs[4] = {d->range, d->count, d->nearest, d->distance_cm};
@@ -165,8 +187,6 @@ inline int check_desc(const Plan &p, const d2pc_sectors_desc *d, char *msg = nul
   }
   return D2PC_OK;
 }
-
-#undef D2PC_SECTORS_REFUSE
 
 // One call as d2pc_sectors.hip's kernels get it (d2pc_sectors_capi.hip fills it).  The stream is a hipStream_t.
 struct Launch {

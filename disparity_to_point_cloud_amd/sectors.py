@@ -201,24 +201,23 @@ def _ptr(x):
     return x.data_ptr() if hasattr(x, "data_ptr") else x
 
 
-class Sectors:
-    """d2pc_sectors_*: one session = one grid geometry (of height or of elevation layers: `layer_kind`) on one device.  `process` takes torch tensors or raw device
-    pointers, is asynchronous on `stream` and allocates nothing."""
+class _Session:
+    """What the two sessions share: a handle of `libd2pc_sectors[_<variant>].so`, made by `<_PREFIX>_create` and given back to
+    `<_PREFIX>_destroy` once."""
 
-    def __init__(self, cfg: SectorsConfig = None, variant=None, **kw):
+    _PREFIX = None
+
+    def _create(self, variant, what, *args):
         self._L, self._h = load_sectors_library(variant), None
-        self.cfg = _set(cfg, kw) if cfg is not None else sectors_config_init(**kw)
         h = ctypes.c_void_p()
-        st = self._L.d2pc_sectors_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        st = getattr(self._L, self._PREFIX + "_create")(*args, ctypes.byref(h))
         if st:
-            raise D2pcError(st, "sectors_create(%d x %d)" % (self.cfg.n_sectors, self.cfg.n_layers))
+            raise D2pcError(st, what)
         self._h = h
-        self.geometry = sectors_geometry(self.cfg)
-        self.n_cells, self.blocks = self.geometry.n_cells, int(self._L.d2pc_sectors_blocks(h))
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.d2pc_sectors_destroy(self._h)
+            getattr(self._L, self._PREFIX + "_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -238,7 +237,20 @@ class Sectors:
         return self._h
 
     def last_error(self) -> str:
-        return self._L.d2pc_sectors_last_error(self._h).decode()
+        return getattr(self._L, self._PREFIX + "_last_error")(self._h).decode()
+
+
+class Sectors(_Session):
+    """d2pc_sectors_*: one session = one grid geometry (of height or of elevation layers: `layer_kind`) on one device.  `process` takes torch tensors or raw device
+    pointers, is asynchronous on `stream` and allocates nothing."""
+
+    _PREFIX = "d2pc_sectors"
+
+    def __init__(self, cfg: SectorsConfig = None, variant=None, **kw):
+        self.cfg = _set(cfg, kw) if cfg is not None else sectors_config_init(**kw)
+        self._create(variant, "sectors_create(%d x %d)" % (self.cfg.n_sectors, self.cfg.n_layers), ctypes.byref(self.cfg))
+        self.geometry = sectors_geometry(self.cfg)
+        self.n_cells, self.blocks = self.geometry.n_cells, int(self._L.d2pc_sectors_blocks(self._h))
 
     def process_desc(self, desc: SectorsDesc, stream_ptr=None):
         """d2pc_sectors_process_device."""
@@ -294,43 +306,17 @@ def sectors_memory_coverage(cfg: SectorsConfig, fovs) -> np.ndarray:
     return out[:n].copy()
 
 
-class SectorsMemory:
+class SectorsMemory(_Session):
     """d2pc_sectors_memory_*: one world-frame point per cell of a grid, kept on the device between calls.  `update` takes
     torch tensors or raw device pointers, is asynchronous on `stream` and allocates nothing."""
 
-    def __init__(self, cfg: SectorsConfig, max_age=OLDEST_AGE):
-        self._L, self._h = load_sectors_library(), None
+    _PREFIX = "d2pc_sectors_memory"
+
+    def __init__(self, cfg: SectorsConfig, max_age=OLDEST_AGE, variant=None):
         self.cfg, self.mcfg = cfg, sectors_memory_config(max_age)
-        h = ctypes.c_void_p()
-        st = self._L.d2pc_sectors_memory_create(ctypes.byref(self.cfg), ctypes.byref(self.mcfg), ctypes.byref(h))
-        if st:
-            raise D2pcError(st, "sectors_memory_create(%d x %d, max_age %d)" % (cfg.n_sectors, cfg.n_layers, max_age))
-        self._h = h
+        self._create(variant, "sectors_memory_create(%d x %d, max_age %d)" % (cfg.n_sectors, cfg.n_layers, max_age),
+                     ctypes.byref(self.cfg), ctypes.byref(self.mcfg))
         self.n_cells = cfg.n_sectors * cfg.n_layers
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.d2pc_sectors_memory_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    @property
-    def handle(self):
-        return self._h
-
-    def last_error(self) -> str:
-        return self._L.d2pc_sectors_memory_last_error(self._h).decode()
 
     def update_desc(self, desc: SectorsMemoryDesc, stream_ptr=None):
         """d2pc_sectors_memory_update_device."""

@@ -12,6 +12,8 @@ import disparity_to_point_cloud_amd as d2pc
 import sectors_elev_ref
 import sectors_memory_ref as mref
 import sectors_ref
+import test_sectors_elevation_gpu as elev
+import test_sectors_gpu as base
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -472,6 +474,101 @@ def test_refusals_enqueue_nothing():
     # and the memory did not advance: the next call ages the seeded record once
     r = h.update(words, 500, dt=4, seen=no_cloud(h.n), what="after the refusals")
     assert r["age"][c] == 4 and (r["age"] != E).sum() == 1
+
+
+# ------------------------------------------------------------------------- the grid and the memory agree on the cell
+RANGE_GATE = dict(axes=(1, 2, 3), r_min=0.5, r_max=25.0)   # rmin2 = 0.25, rmax2 = 625
+AGREE = {
+    "72x1": dict(n_sectors=72, **RANGE_GATE),
+    "8x3": dict(n_sectors=8, n_layers=3, u_min=-0.7, u_max=1.9, azimuth0=0.3, **RANGE_GATE),
+    "60x30e": dict(n_sectors=60, n_layers=30, layer_kind=1, u_min=-HALF_PI, u_max=HALF_PI, azimuth0=-np.pi / 60, **RANGE_GATE),
+    "90x64e": dict(n_sectors=90, n_layers=64, layer_kind=1, u_min=-1.2, u_max=1.4, **RANGE_GATE),   # two carry passes
+}
+CARRY_PASS = 1024 * 3    # records of a carry pass: the block's lanes x the records a lane re-bins
+
+
+def thinned(a, most):
+    return a[::-(-len(a) // most)]
+
+
+def agree_cloud(sec, ref):
+    """Points on and next to the azimuth boundaries with l = +-0 and f < 0 among them, on the range gates' bit patterns, on
+    the band's two boundaries and the layers' (elevation boundaries or slab edges), and a random cloud: the builders of
+    tests/test_sectors_gpu.py and tests/test_sectors_elevation_gpu.py, thinned to a few thousand points."""
+    axes, g = (1, 2, 3), sec.geometry
+    elevation = sec.cfg.layer_kind == d2pc.LAYERS_ELEVATION
+    xyz = [thinned(base.boundary_points(ref, axes), 1500)]
+    lo, hi = elev.bits(g.rmin2), elev.bits(g.rmax2)
+    for b in (lo - 1, lo, lo + 1, hi - 1, hi, hi + 1):
+        fl = base.on_circle(b, seed=b & 0xFFFF)
+        xyz.append(base.from_flu(axes, fl[:, 0], fl[:, 1], np.zeros(len(fl))))
+        if elevation:
+            xyz.append(elev.on_sphere(b, seed=b & 0xFFF))
+    if elevation:
+        xyz.append(thinned(elev.boundary_points(ref), 1500))
+    else:
+        edges = [F32(sec.cfg.u_min), F32(sec.cfg.u_max)] + [F32(F32(sec.cfg.u_min) + F32(k) / F32(g.inv_h)) for k in range(1, sec.cfg.n_layers)]
+        us = np.array([v for e in edges if np.isfinite(e) for v in (np.nextafter(e, F32(-np.inf)), e, np.nextafter(e, F32(np.inf)))], dtype=F32)
+        xyz.append(base.from_flu(axes, np.full(len(us), 2.0), np.linspace(-3, 3, len(us)), us))
+    xyz.append(base.random_xyz(600, seed=77, spread=8.0))
+    return np.concatenate(xyz).astype(F32)
+
+
+@pytest.mark.parametrize("name", list(AGREE))
+def test_a_remembered_point_lands_in_the_cell_the_grid_puts_it_in(name):
+    """The two kernels against each other, not each against its own model.  A memory is seeded with a cloud's points (one
+    per cell, as many cells at a time as the grid has), updated once more with no cloud, a pose, no `covered` and the
+    largest max_age; the carried points R^T (w - t), formed on the host from the records the device stored with the
+    reference's float arithmetic, go through an ordinary sectors call.  The cells that hold something and every range
+    word of the two device results are the same bits.  Twice: under a yaw, pitch, roll and translation, and under the
+    identity, where the carried points are the seeds themselves, on their boundaries."""
+    sec = d2pc.Sectors(**AGREE[name])
+    mem = d2pc.SectorsMemory(sec.cfg, d2pc.sectors.OLDEST_AGE)
+    ref, n = grid_ref(sec.cfg), sec.n_cells
+    model = mref.SectorsMemoryRef(ref, d2pc.sectors.OLDEST_AGE)
+    cloud = agree_cloud(sec, ref)
+    assert 500 < len(cloud) <= 4500
+    part = ref.cells(cloud)[0]
+    assert part.sum() > 100 and (~part).sum() > 100, "the cloud lies on both sides of the gates"
+    step = torch.zeros(16, dtype=torch.int32, device=DEV)
+    poses = [(yaw_pose((1, 2, 3), 0.6458, 0.03, -0.02), np.array([0.4, -0.1, 0.9]), 7), (EYE, ZERO, 1)]
+    held = second_pass = 0
+    for R, t, dt in poses:
+        for first in range(0, len(cloud), n):
+            batch = cloud[first:first + n]
+            m = len(batch)
+            cells = np.arange(m) * n // m           # spread over the whole table: records of both carry passes
+            count, nearest = no_cloud(n)
+            count[cells], nearest[cells] = 1, np.arange(m)
+            pts = dev_words(records(batch, seed=first))
+            mem.reset(stream())
+            step.copy_(dev_words(d2pc.sectors_memory_step(EYE, ZERO, 0)))
+            seeded = fresh_outputs(n, ("records",))
+            mem.update(pts, m, dev_words(count), dev_words(nearest), step, stream_ptr=stream(), **seeded)
+            torch.cuda.synchronize()
+            rec = read_outputs(seeded, n)["records"].reshape(n, 4)
+            assert np.array_equal(np.flatnonzero(rec[:, 3] != E), cells), "the seeds are in the memory"
+            # the update under test: nothing seen, everything carried
+            step.copy_(dev_words(d2pc.sectors_memory_step(R, t, dt)))
+            out = fresh_outputs(n, ("range", "age"))
+            mem.update(pts, m, dev_words(no_cloud(n)[0]), dev_words(no_cloud(n)[1]), step, stream_ptr=stream(), **out)
+            torch.cuda.synchronize()
+            got = read_outputs(out, n)
+            # the carried points, as records of a cloud of their own, through the grid's kernel
+            carried = model.to_points_frame(rec[cells, :3].copy().view(F32), R, t)
+            grid = base.run(sec, dev_words(records(carried, seed=first + 1)), m, want=("range", "count"))
+            what = "%s, points %d.., dt %d" % (name, first, dt)
+            assert np.array_equal(got["age"] != E, grid["count"] > 0), what + ": the cells that hold something"
+            bad = np.flatnonzero(got["range"] != grid["range"])
+            assert bad.size == 0, "%s: range of cell %d is 0x%x from the memory, 0x%x from the grid (%d differ)" % (
+                what, bad[0], got["range"][bad[0]], grid["range"][bad[0]], bad.size)
+            assert np.all(got["age"][got["age"] != E] == dt)
+            held += int((got["age"] != E).sum())
+            second_pass += int(ref.cells(carried)[0][cells >= CARRY_PASS].sum())
+    assert held > 100, "the memory held nothing to compare"
+    assert (second_pass > 0) == (n > CARRY_PASS), "the second carry pass took part exactly where the table needs it"
+    mem.close()
+    sec.close()
 
 
 # ------------------------------------------------------------------------------------- behind the producer, in a graph

@@ -31,6 +31,13 @@ ranks them).  GPU box only.
                                             the update, beside S and S0 of the same session, on the one-camera frame and on the
                                             rig's merged cloud, for 72 x 1 and 60 x 30 elevation, in ONE interleaved run.  No time
                                             is fixed in advance: the yardstick is S0, the sectors' own fixed part, in the same run
+  python tools/sectors_bench.py --parent NAME
+                                        ->  profiles/sectors_refactor_bench.txt: this build against libd2pc_sectors_NAME.so, a build
+                                            of the parent commit's sources (`make sectors SNAME=NAME` there), when a change must move
+                                            neither a byte nor the time: S of 72 x 1, 360 x 16 height, 72 x 16 and 60 x 30 elevation
+                                            and M of 72 x 1 and 60 x 30 elevation on the rig's merged cloud, the outputs of the two
+                                            builds compared bit for bit first, all twelve arms in ONE interleaved run; a row's new
+                                            median may exceed the parent's by no more than the arms' spread in that run
 """
 import argparse
 import os
@@ -297,16 +304,102 @@ def elevation(a):
         if a.parent:
             lines.append("# the height instantiation against libd2pc_sectors_%s.so: new may be slower by no more than the larger of the two arms'" % a.parent)
             lines.append("# (max - min) / median in this run")
-            lines.append("%-20s %-30s %-30s %10s %10s %s" % ("grid", "new", "parent", "new/parent", "allowed", "verdict"))
-            for label, _ in versus:
-                new, old = t[label + " new"], t[label + " parent"]
-                spread = max((max(v) - min(v)) / float(np.median(v)) for v in (new, old))
-                ratio = med[label + " new"] / med[label + " parent"]
-                lines.append("%-20s %-30s %-30s %10.4f %10.4f %s" % (label, fmt(new), fmt(old), ratio, 1.0 + spread,
-                                                                     "ok" if ratio <= 1.0 + spread else "SLOWER"))
+            lines += verdicts(t, [label for label, _ in versus])
         for sec, _ in sessions:
             sec.close()
         prod.close()
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
+def verdicts(t, rows):
+    """The table of `row new` against `row parent` of the timings t: the project's rule for a build against its parent."""
+    lines = ["%-24s %-30s %-30s %10s %10s %s" % ("row", "new", "parent", "new/parent", "allowed", "verdict")]
+    for row in rows:
+        new, old = t[row + " new"], t[row + " parent"]
+        spread = max((max(v) - min(v)) / float(np.median(v)) for v in (new, old))
+        ratio = float(np.median(new)) / float(np.median(old))
+        lines.append("%-24s %-30s %-30s %10.4f %10.4f %s" % (row, fmt(new), fmt(old), ratio, 1.0 + spread, "ok" if ratio <= 1.0 + spread else "SLOWER"))
+    return lines
+
+
+def parent(a):
+    """This build against libd2pc_sectors_<parent>.so on the rig's merged cloud: S of four grids and M of two, the outputs
+    of the two builds compared bit for bit first, then all twelve arms interleaved in one run."""
+    prop = torch.cuda.get_device_properties(0)
+    half_pi = float(np.float32(np.pi / 2))
+    histogram = dict(n_sectors=60, n_layers=30, u_min=-half_pi, u_max=half_pi, azimuth0=-np.pi / 60, layer_kind=d2pc.LAYERS_ELEVATION)
+    s_rows = [("S 72 x 1 height", dict()), ("S 360 x 16 height", dict(n_sectors=360, n_layers=16, u_min=-40.0, u_max=40.0)),
+              ("S 72 x 16 elevation", dict(n_sectors=72, n_layers=16, u_min=-half_pi, u_max=half_pi, layer_kind=d2pc.LAYERS_ELEVATION)),
+              ("S 60 x 30 elevation", histogram)]
+    m_rows = [("M 72 x 1 height", dict()), ("M 60 x 30 elevation", histogram)]
+    lines = ["# tools/sectors_bench.py --parent %s --rounds %d --iters %d" % (a.parent, a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round)" % (
+                 prop.name, prop.multi_processor_count),
+             "# new = libd2pc_sectors.so, parent = libd2pc_sectors_%s.so (`make sectors SNAME=%s` of the parent commit's sources), on the" % (a.parent, a.parent),
+             "# 16-camera rig's merged cloud.  S = d2pc_sectors_process_device alone (range + count); M = d2pc_sectors_memory_update_device",
+             "# alone (range, distance_cm, age; a 37-degree yaw, a translation and dt 50 every call, max_age 2,000, a forward field of",
+             "# view as `covered`).  The two builds' outputs of every row were compared bit for bit before the timing.  us per call:",
+             "# median (min .. max).  new may be slower by no more than the larger of the two arms' (max - min) / median in this run"]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    name, n, w, h, mode, rig_case, holes = CASES[1]
+    with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx:
+        prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+        prod(s)
+        torch.cuda.synchronize()
+        ctx.check_async_error()
+        npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n])
+        cloud = prod.pts[:npts].clone()
+        prod.close()
+    R = np.array([[np.cos(0.6458), 0.0, np.sin(0.6458)], [0.0, 1.0, 0.0], [-np.sin(0.6458), 0.0, np.cos(0.6458)]])   # about the optical y
+    step = torch.from_numpy(d2pc.sectors_memory_step(R, [0.4, -0.1, 0.9], 50).view(np.int32).copy()).to("cuda")
+    arms, labels, pairs, keep = [], [], [], []
+    for row, grid in s_rows:
+        outs = []
+        for which, variant in (("new", None), ("parent", a.parent)):
+            sec = d2pc.Sectors(variant=variant, **grid)
+            out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
+                       count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+            keep.append(sec)
+            outs.append(out)
+            arms.append(lambda sec=sec, out=out: sec.process(cloud, npts, stream_ptr=s, **out))
+            labels.append("%s %s" % (row, which))
+        pairs.append((row, outs))
+    for row, grid in m_rows:
+        sec = d2pc.Sectors(**grid)
+        seen = dict(count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                    nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+        sec.process(cloud, npts, stream_ptr=s, **seen)
+        cov = torch.from_numpy(d2pc.sectors_memory_coverage(sec.cfg, [(0.0, 0.0, 1.5, 1.0, 0.05)])).to("cuda")
+        keep += [sec, seen, cov]
+        outs = []
+        for which, variant in (("new", None), ("parent", a.parent)):
+            mem = d2pc.SectorsMemory(sec.cfg, 2000, variant=variant)
+            out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
+                       distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"),
+                       age=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+            keep.append(mem)
+            outs.append(out)
+            arms.append(lambda mem=mem, seen=seen, cov=cov, out=out: mem.update(cloud, npts, seen["count"], seen["nearest"], step, covered=cov,
+                                                                                stream_ptr=s, **out))
+            labels.append("%s %s" % (row, which))
+        pairs.append((row, outs))
+    for _ in range(3):   # warm-up: code objects; three updates, so that the memories carry, age and drop
+        for fn in arms:
+            fn()
+        torch.cuda.synchronize()
+        for row, (new, old) in pairs:   # (the memories of the two builds advance in step: the same number of calls)
+            assert all(torch.equal(new[k].view(torch.int32) if new[k].dtype == torch.float32 else new[k],
+                                   old[k].view(torch.int32) if old[k].dtype == torch.float32 else old[k]) for k in new), row + ": the builds disagree"
+    iters = int(min(max(a.iters, 30000.0 / timed(arms[0], 5)), 4000))   # (a sectors arm: no memory advances alone)
+    t = dict(zip(labels, interleaved(arms, a.rounds, iters)))
+    lines.append("# %d points, %.1f MB read by S, %d calls per timed window" % (npts, 16 * npts / 1e6, iters))
+    lines += verdicts(t, [row for row, _ in pairs])
+    for x in keep:
+        if hasattr(x, "close"):
+            x.close()
     for ln in lines:
         print(ln, flush=True)
     return lines
@@ -401,11 +494,15 @@ def main():
     ap.add_argument("--ab", action="store_true", help="the A/B of the in-wave reduction instead of the cost table")
     ap.add_argument("--elevation", action="store_true", help="elevation layers beside height layers instead of the cost table")
     ap.add_argument("--memory", action="store_true", help="the memory's update beside the sectors call instead of the cost table")
-    ap.add_argument("--parent", default=None, help="with --elevation: libd2pc_sectors_<PARENT>.so, an earlier build, for the height rows")
+    ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
+                    "alone, the table of this build against it (S of four grids, M of two)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    out = a.out or os.path.join(ROOT, "profiles", "sectors_memory_bench.txt" if a.memory else "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_bench.txt")
-    lines = memory(a) if a.memory else elevation(a) if a.elevation else ab(a) if a.ab else bench(a)
+    if a.parent and (a.memory or a.ab):
+        ap.error("--parent goes with --elevation or stands alone (its own table holds the memory's rows)")
+    versus = bool(a.parent) and not (a.memory or a.elevation or a.ab)
+    out = a.out or os.path.join(ROOT, "profiles", "sectors_memory_bench.txt" if a.memory else "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_refactor_bench.txt" if versus else "sectors_bench.txt")
+    lines = memory(a) if a.memory else elevation(a) if a.elevation else ab(a) if a.ab else parent(a) if versus else bench(a)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")

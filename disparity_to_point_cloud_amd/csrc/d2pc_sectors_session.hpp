@@ -1,6 +1,7 @@
-// d2pc_sectors_session.hpp -- what the two sessions of include/d2pc_sectors.h (d2pc_sectors_capi.hip,
-// d2pc_sectors_memory_capi.hip) share on the host and need the HIP runtime for: selecting the session's device, the
-// device-id check, the boundary tables in device memory and a session's error string.  (The plan headers stay free of HIP.)
+// d2pc_sectors_session.hpp -- what the sessions of include/d2pc_sectors.h (d2pc_sectors_capi.hip,
+// d2pc_sectors_memory_capi.hip, d2pc_sectors_steer_capi.hip) share on the host and need the HIP runtime for: selecting the
+// session's device, the device-id check, the boundary tables in device memory (the grid's and the memory's; the steer
+// uploads its own reach tables) and a session's error string.  (The plan headers stay free of HIP.)
 #pragma once
 #include <hip/hip_runtime.h>
 

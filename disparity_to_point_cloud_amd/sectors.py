@@ -25,8 +25,15 @@ SECTORS_SYMBOLS = [
     "d2pc_sectors_memory_create", "d2pc_sectors_memory_destroy", "d2pc_sectors_memory_last_error", "d2pc_sectors_memory_desc_init",
     "d2pc_sectors_memory_desc_check", "d2pc_sectors_memory_update_device", "d2pc_sectors_memory_reset_device",
     "d2pc_sectors_memory_coverage",
+    "d2pc_sectors_steer_config_init", "d2pc_sectors_steer_reach", "d2pc_sectors_steer_goal_cell", "d2pc_sectors_steer_create",
+    "d2pc_sectors_steer_destroy", "d2pc_sectors_steer_last_error", "d2pc_sectors_steer_desc_init", "d2pc_sectors_steer_desc_check",
+    "d2pc_sectors_steer_device",
 ]
 EMPTY_AGE, OLDEST_AGE = 0xFFFFFFFF, 0xFFFFFFFE   # the age word of an empty record; where an age saturates
+STEER_MAX_REACH_SECTORS, STEER_MAX_REACH_LAYERS, STEER_MAX_CANDIDATES, STEER_MAX_WEIGHT = 32, 16, 32, 4095
+STEER_OFF = 0xFFFFFFFF            # a goal_sector / prev_sector that switches its term off
+STEER_NO_CANDIDATE = 0xFFFFFFFFFFFFFFFF   # a candidate slot beyond the free cells
+STEER_BLOCKED = 0xFFFFFFFF        # the cost of a cell that is not free
 
 
 class SectorsConfig(ctypes.Structure):
@@ -76,6 +83,32 @@ class SectorsMemoryDesc(ctypes.Structure):
         ("points_frame_stride_points", ctypes.c_size_t), ("count", ctypes.c_void_p), ("nearest", ctypes.c_void_p),
         ("step", ctypes.c_void_p), ("covered", ctypes.c_void_p), ("range", ctypes.c_void_p), ("distance_cm", ctypes.c_void_p),
         ("age", ctypes.c_void_p), ("records", ctypes.c_void_p),
+    ]
+
+
+class SectorsSteerConfig(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("radius", ctypes.c_float), ("max_reach_sectors", ctypes.c_int32),
+        ("max_reach_layers", ctypes.c_int32), ("free_cm", ctypes.c_uint32), ("min_clearance_cm", ctypes.c_uint32),
+        ("horizon_cm", ctypes.c_uint32), ("w_goal", ctypes.c_uint32), ("w_prev", ctypes.c_uint32), ("w_near", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
+class SectorsSteerStep(ctypes.Structure):   # 32 bytes, in device memory
+    _fields_ = [("goal_sector", ctypes.c_uint32), ("goal_layer", ctypes.c_uint32), ("prev_sector", ctypes.c_uint32),
+                ("prev_layer", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+class SectorsSteerCandidate(ctypes.Structure):   # as a little-endian uint64: (cost << 32) | cell
+    _fields_ = [("cell", ctypes.c_uint32), ("cost", ctypes.c_uint32)]
+
+
+class SectorsSteerDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("n_candidates", ctypes.c_int32), ("distance_cm", ctypes.c_void_p),
+        ("allowed", ctypes.c_void_p), ("step", ctypes.c_void_p), ("clearance_cm", ctypes.c_void_p), ("cost", ctypes.c_void_p),
+        ("candidates", ctypes.c_void_p), ("summary", ctypes.c_void_p),
     ]
 
 
@@ -132,6 +165,21 @@ def load_sectors_library(variant=None):
         L.d2pc_sectors_memory_update_device.argtypes = [vp, mdesc, vp]
         L.d2pc_sectors_memory_reset_device.argtypes = [vp, vp]
         L.d2pc_sectors_memory_coverage.argtypes = [cfg, ctypes.POINTER(SectorsFov), ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int]
+    if variant is None or hasattr(L, "d2pc_sectors_steer_create"):   # (an A/B variant may be a build from before the steer)
+        scfg, sdesc, u16 = ctypes.POINTER(SectorsSteerConfig), ctypes.POINTER(SectorsSteerDesc), ctypes.POINTER(ctypes.c_uint16)
+        u32 = ctypes.POINTER(ctypes.c_uint32)
+        L.d2pc_sectors_steer_config_init.argtypes = [scfg]
+        L.d2pc_sectors_steer_config_init.restype = None
+        L.d2pc_sectors_steer_reach.argtypes = [cfg, scfg, u16, ctypes.c_int, u16, ctypes.c_int]
+        L.d2pc_sectors_steer_goal_cell.argtypes = [cfg, ctypes.c_double, ctypes.c_double, u32, u32]
+        L.d2pc_sectors_steer_create.argtypes = [cfg, scfg, ctypes.POINTER(vp)]
+        L.d2pc_sectors_steer_destroy.argtypes = [vp]
+        L.d2pc_sectors_steer_last_error.argtypes = [vp]
+        L.d2pc_sectors_steer_last_error.restype = ctypes.c_char_p
+        L.d2pc_sectors_steer_desc_init.argtypes = [sdesc]
+        L.d2pc_sectors_steer_desc_init.restype = None
+        L.d2pc_sectors_steer_desc_check.argtypes = [cfg, scfg, sdesc]
+        L.d2pc_sectors_steer_device.argtypes = [vp, sdesc, vp]
     if variant is None:
         _lib = L
     return L
@@ -202,7 +250,7 @@ def _ptr(x):
 
 
 class _Session:
-    """What the two sessions share: a handle of `libd2pc_sectors[_<variant>].so`, made by `<_PREFIX>_create` and given back to
+    """What the sessions share: a handle of `libd2pc_sectors[_<variant>].so`, made by `<_PREFIX>_create` and given back to
     `<_PREFIX>_destroy` once."""
 
     _PREFIX = None
@@ -338,3 +386,76 @@ class SectorsMemory(_Session):
         st = self._L.d2pc_sectors_memory_reset_device(self._h, stream_ptr)
         if st:
             raise D2pcError(st, self.last_error())
+
+
+def sectors_steer_config_init(**kw) -> SectorsSteerConfig:
+    """d2pc_sectors_steer_config_init, then the given fields."""
+    c = SectorsSteerConfig()
+    load_sectors_library().d2pc_sectors_steer_config_init(ctypes.byref(c))
+    return _set(c, kw)
+
+
+def sectors_steer_desc_init(**kw) -> SectorsSteerDesc:
+    """d2pc_sectors_steer_desc_init, then the given fields."""
+    d = SectorsSteerDesc()
+    load_sectors_library().d2pc_sectors_steer_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_steer_desc_check(cfg: SectorsConfig, scfg: SectorsSteerConfig, desc: SectorsSteerDesc) -> int:
+    """d2pc_sectors_steer_desc_check: the status d2pc_sectors_steer_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_steer_desc_check(ctypes.byref(cfg), ctypes.byref(scfg), ctypes.byref(desc))
+
+
+def sectors_steer_reach(cfg: SectorsConfig, scfg: SectorsSteerConfig):
+    """d2pc_sectors_steer_reach: (reach_s uint16 (n_layers, Wa + 1), reach_l uint16 (We + 1))."""
+    rs = np.zeros(MAX_ELEVATION_LAYERS * (STEER_MAX_REACH_SECTORS + 1), dtype=np.uint16)
+    rl = np.zeros(STEER_MAX_REACH_LAYERS + 1, dtype=np.uint16)
+    u16 = ctypes.POINTER(ctypes.c_uint16)
+    n = load_sectors_library().d2pc_sectors_steer_reach(ctypes.byref(cfg), ctypes.byref(scfg), rs.ctypes.data_as(u16), len(rs),
+                                                        rl.ctypes.data_as(u16), len(rl))
+    if n <= 0:
+        raise D2pcError(-n, "sectors_steer_reach(%d x %d, reach %d / %d)" % (cfg.n_sectors, cfg.n_layers, scfg.max_reach_sectors,
+                                                                           scfg.max_reach_layers))
+    return rs[:n].reshape(cfg.n_layers, scfg.max_reach_sectors + 1).copy(), rl[:scfg.max_reach_layers + 1].copy()
+
+
+def sectors_steer_goal_cell(cfg: SectorsConfig, yaw, pitch_or_layer=0.0):
+    """d2pc_sectors_steer_goal_cell: (sector, layer) of a direction; raises D2pcError as the C function refuses."""
+    s, l = ctypes.c_uint32(), ctypes.c_uint32()
+    st = load_sectors_library().d2pc_sectors_steer_goal_cell(ctypes.byref(cfg), yaw, pitch_or_layer, ctypes.byref(s), ctypes.byref(l))
+    if st:
+        raise D2pcError(st, "sectors_steer_goal_cell(%r, %r)" % (yaw, pitch_or_layer))
+    return s.value, l.value
+
+
+def sectors_steer_step(goal_sector=STEER_OFF, goal_layer=0, prev_sector=STEER_OFF, prev_layer=0) -> np.ndarray:
+    """The 8 words of a d2pc_sectors_steer_step as uint32, to copy to the device."""
+    return np.array([goal_sector, goal_layer, prev_sector, prev_layer, 0, 0, 0, 0], dtype=np.uint64).astype(np.uint32)
+
+
+class SectorsSteer(_Session):
+    """d2pc_sectors_steer_*: clearance, cost and the best free cells of a grid's distance_cm, in one launch.  `steer` takes
+    torch tensors or raw device pointers, is asynchronous on `stream` and allocates nothing."""
+
+    _PREFIX = "d2pc_sectors_steer"
+
+    def __init__(self, cfg: SectorsConfig, scfg: SectorsSteerConfig = None, variant=None, **kw):
+        self.cfg = cfg
+        self.scfg = _set(scfg, kw) if scfg is not None else sectors_steer_config_init(**kw)
+        self._create(variant, "sectors_steer_create(%d x %d, reach %d / %d)" % (
+            cfg.n_sectors, cfg.n_layers, self.scfg.max_reach_sectors, self.scfg.max_reach_layers), ctypes.byref(self.cfg), ctypes.byref(self.scfg))
+        self.n_cells = cfg.n_sectors * cfg.n_layers
+
+    def steer_desc(self, desc: SectorsSteerDesc, stream_ptr=None):
+        """d2pc_sectors_steer_device."""
+        st = self._L.d2pc_sectors_steer_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def steer(self, distance_cm, step, allowed=None, clearance_cm=None, cost=None, candidates=None, n_candidates=1, summary=None,
+              stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.steer_desc(sectors_steer_desc_init(
+            n_candidates=n_candidates, distance_cm=_ptr(distance_cm), allowed=_ptr(allowed), step=_ptr(step),
+            clearance_cm=_ptr(clearance_cm), cost=_ptr(cost), candidates=_ptr(candidates), summary=_ptr(summary)), stream_ptr)

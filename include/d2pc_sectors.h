@@ -121,6 +121,53 @@
  *     otherwise          the empty record; range = +inf
  * distance_cm is formed from range as above, no_obstacle_cm where the record is empty; age[c] is the record's age word.
  * The new records replace the old as one step: no carry reads a record this call wrote.
+ *
+ * --------------------------------------------------------------------------------------- STEER (d2pc_sectors_steer_*)
+ * What a consumer of the grid does first: widen every obstacle by the vehicle's radius (VFH+'s enlargement), mask the
+ * directions that are no longer free and rank the free ones against a goal direction, the previous heading and the
+ * clearance.  d2pc_sectors_steer_device does it in one launch from a grid's distance_cm, as d2pc_sectors_process_device
+ * or d2pc_sectors_memory_update_device wrote it, for either layer kind.  All integers: nothing is rounded on the device.
+ * tests/sectors_steer_ref.py restates it in numpy.
+ *
+ * Grid.  n = n_sectors, L = n_layers, cell (s, l) = l * n + s.  Sectors wrap around; layers do not (no over-the-pole
+ * neighbour).
+ *
+ * Input.  d[c] = distance_cm[c]; a value >= free_cm is read as 65535, nothing there (a no_obstacle_cm that is not 65535).
+ *
+ * Reach tables, made once on the host in double (d2pc_sectors_steer_reach returns them).  rho = (double)radius (the
+ * vehicle's radius plus margin), alpha = 2 pi / n, Wa = max_reach_sectors, We = max_reach_layers, and
+ *     reach(theta) = min(65534, floor(100 rho / sin(theta)))  for 0 < theta < pi/2,
+ *                    min(65534, floor(100 rho))               for theta >= pi/2    (65534 for a theta that is not > 0)
+ *     reach_s[i][0] = reach_l[0] = 65535                      (a cell always sees itself)
+ *     reach_s[i][k] = reach((k - 1/2) alpha cos_i), k = 1 .. Wa, indexed by the layer i of the OBSTACLE's cell:
+ *                     cos_i = 1 for height layers; cos(e_i + eps/2) for elevation layers, with e_i as the elevation
+ *                     table forms it and eps = ((double)u_max - (double)u_min) / L (an obstacle near the pole spans
+ *                     more sectors)
+ *     reach_l[k],  k = 1 .. We:  elevation layers reach((k - 1/2) eps);  height layers 65534 if (k - 1/2) eps < rho,
+ *                     otherwise 0 (eps is the slab's height then)
+ *
+ * Clearance.  clearance_cm[(s, l)] = the minimum of d[((s + ks) mod n, l + kl)] over |ks| <= Wa, |kl| <= We,
+ * 0 <= l + kl < L, of the values v with v <= reach_l[|kl|] and v <= reach_s[l + kl][|ks|]; 65535 if none qualifies.
+ * This 2-D window is the definition.  Because reach_s is indexed by the source's layer it equals an azimuth pass per
+ * layer followed by a layer pass over the first pass's minima, which is what the kernel does.
+ *
+ * Free.  A cell is free when clearance_cm >= min_clearance_cm and (`allowed` is NULL or allowed[c] != 0).
+ *
+ * Step (d2pc_sectors_steer_step, 32 bytes in DEVICE memory).  A sector >= n (0xFFFFFFFF by convention) switches that term
+ * off; a layer >= L is clamped to L - 1.  The kernel refuses nothing.
+ *
+ * Cost of a free cell, in uint32 (it cannot wrap: the weights are <= 4095):
+ *     cost = w_goal * D(c, goal) + w_prev * D(c, prev) + w_near * (horizon_cm - min(clearance_cm[c], horizon_cm))
+ *     D((s, l), (s', l')) = min(|s - s'|, n - |s - s'|) + |l - l'|
+ * A cell that is not free has the cost 0xFFFFFFFF.
+ *
+ * Outputs, all nullable but one:
+ *     clearance_cm  uint16 x n_cells
+ *     cost          uint32 x n_cells
+ *     candidates    n_candidates records {cell, cost}: as a little-endian uint64 a record is the key (cost << 32) | cell.
+ *                   The list holds the smallest keys among the free cells, ascending: ties in cost go to the smaller
+ *                   cell, whatever order the device visits the cells in.  Slots beyond the free cells hold all ones
+ *     summary       uint32 x 4: the number of free cells, the smallest d after the free_cm mapping (65535 if none), 0, 0
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -306,6 +353,89 @@ int d2pc_sectors_memory_reset_device(d2pc_sectors_memory *m, void *stream);
  */
 int d2pc_sectors_memory_coverage(const d2pc_sectors_config *grid, const d2pc_sectors_fov *fovs, int n_fovs,
                                  uint8_t *covered_host, int capacity);
+
+/* -------------------------------------------------------------------------------------------------------- the steer */
+#define D2PC_SECTORS_STEER_MAX_REACH_SECTORS 32
+#define D2PC_SECTORS_STEER_MAX_REACH_LAYERS 16
+#define D2PC_SECTORS_STEER_MAX_CANDIDATES 32
+#define D2PC_SECTORS_STEER_MAX_WEIGHT 4095
+#define D2PC_SECTORS_STEER_OFF 0xFFFFFFFFu   /* a goal_sector / prev_sector that switches its term off (any value >= n_sectors does) */
+
+typedef struct d2pc_sectors_steer_config {   /* fixed for a steer session, beside the grid's d2pc_sectors_config */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_steer_config) */
+  float radius;                /* the vehicle's radius plus margin, in the cloud's unit (metres); finite and > 0 */
+  int32_t max_reach_sectors;   /* Wa: 0 .. 32 and <= n_sectors / 2 */
+  int32_t max_reach_layers;    /* We: 0 .. 16 and <= n_layers - 1 */
+  uint32_t free_cm;            /* <= 65535: a distance_cm at or above it is nothing there */
+  uint32_t min_clearance_cm;   /* <= 65535: a cell is free from this clearance on */
+  uint32_t horizon_cm;         /* <= 65535: clearance beyond it costs nothing */
+  uint32_t w_goal, w_prev, w_near;   /* <= 4095 each */
+  uint32_t reserved[2];        /* zero */
+} d2pc_sectors_steer_config;
+/* radius 0.5, reach 8 sectors / 0 layers, free_cm 65535, min_clearance_cm 100, horizon_cm 1000, weights 16 / 4 / 1. */
+void d2pc_sectors_steer_config_init(d2pc_sectors_steer_config *scfg);
+
+typedef struct d2pc_sectors_steer_step {   /* 32 bytes in DEVICE memory: a captured graph replays with a new goal after one small copy */
+  uint32_t goal_sector, goal_layer;   /* a sector >= n_sectors switches the term off; a layer >= n_layers is n_layers - 1 */
+  uint32_t prev_sector, prev_layer;   /* the previous heading, likewise */
+  uint32_t reserved[4];
+} d2pc_sectors_steer_step;
+
+typedef struct d2pc_sectors_steer_candidate {   /* as a little-endian uint64: (cost << 32) | cell */
+  uint32_t cell, cost;
+} d2pc_sectors_steer_candidate;
+
+/* Host only: the reach tables.  reach_sectors gets n_layers x (Wa + 1) entries, row i = reach_s[i][0 .. Wa];
+ * reach_layers gets We + 1.  Returns the entries of reach_sectors (reach_layers' are max_reach_layers + 1), or the
+ * negated d2pc_status: of the refusal of `grid` or `scfg` as d2pc_sectors_steer_desc_check makes them,
+ * D2PC_ERR_INVALID_ARG for a NULL table, D2PC_ERR_CAPACITY when a capacity (in entries) is too small. */
+int d2pc_sectors_steer_reach(const d2pc_sectors_config *grid, const d2pc_sectors_steer_config *scfg, uint16_t *reach_sectors,
+                             int sectors_capacity, uint16_t *reach_layers, int layers_capacity);
+/* Host only, in double: the cell of a direction, for a step.  sector = floor(wrap(yaw - azimuth0) / alpha) with wrap
+ * into [0, 2 pi).  Elevation layers: the layer is the number of i in 1 .. n_layers - 1 with pitch >= e_i;
+ * D2PC_ERR_INVALID_ARG for a pitch outside [e_0, e_L).  Height layers: the third argument is the layer itself, floored;
+ * D2PC_ERR_INVALID_ARG outside [0, n_layers).  D2PC_ERR_INVALID_ARG also for NULL or a direction that is not finite. */
+int d2pc_sectors_steer_goal_cell(const d2pc_sectors_config *grid, double yaw, double pitch_or_layer, uint32_t *sector,
+                                 uint32_t *layer);
+
+typedef struct d2pc_sectors_steer d2pc_sectors_steer;
+/* Refuses what d2pc_sectors_steer_desc_check refuses of `grid` and `scfg`.  Allocates the two reach tables on the device
+ * and nothing else, ever.  D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
+int d2pc_sectors_steer_create(const d2pc_sectors_config *grid, const d2pc_sectors_steer_config *scfg, d2pc_sectors_steer **out);
+int d2pc_sectors_steer_destroy(d2pc_sectors_steer *s);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_steer_last_error(const d2pc_sectors_steer *s);
+
+typedef struct d2pc_sectors_steer_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_steer_desc) */
+  int32_t n_candidates;        /* 1 .. 32 when `candidates` is given */
+  const uint16_t *distance_cm; /* DEVICE: n_cells, as d2pc_sectors_process_device or d2pc_sectors_memory_update_device wrote them */
+  const uint8_t *allowed;      /* DEVICE, nullable: one byte per cell, zero = not to be steered into (d2pc_sectors_memory_coverage
+                                  makes such a mask) */
+  const d2pc_sectors_steer_step *step;   /* DEVICE, 4-byte aligned */
+  uint16_t *clearance_cm;      /* DEVICE out, nullable; at least one of the four is given */
+  uint32_t *cost;
+  d2pc_sectors_steer_candidate *candidates;   /* n_candidates records, 8-byte aligned */
+  uint32_t *summary;           /* 4 words */
+} d2pc_sectors_steer_desc;
+/* struct_size, n_candidates 1; everything else zero. */
+void d2pc_sectors_steer_desc_init(d2pc_sectors_steer_desc *desc);
+/* Host only: what d2pc_sectors_steer_device refuses, without a session.  First the refusals of `grid` with the grid's
+ * statuses, then the steer configuration's -- D2PC_ERR_INVALID_ARG: NULL, struct_size, a radius that is NaN, zero, negative
+ * or not finite, a weight > 4095, a *_cm > 65535; D2PC_ERR_BAD_SIZE: a reach that is negative or above its cap,
+ * max_reach_sectors > n_sectors / 2, max_reach_layers > n_layers - 1 (or > 0 without a finite height band) -- then the
+ * descriptor's, all D2PC_ERR_INVALID_ARG: NULL, struct_size, a NULL distance_cm or step, no output, n_candidates out of
+ * 1 .. 32 when candidates is given, a pointer not aligned to its type (8 bytes for candidates), an output that overlaps
+ * distance_cm, allowed, step or another output. */
+int d2pc_sectors_steer_desc_check(const d2pc_sectors_config *grid, const d2pc_sectors_steer_config *scfg,
+                                  const d2pc_sectors_steer_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): ONE launch of one block, no memset, no allocation, no host
+ * read -- it can be captured into a graph behind d2pc_sectors_process_device or d2pc_sectors_memory_update_device.  Every
+ * refusal is made before anything is enqueued.  Bit-reproducible: every value is an integer and every minimum is of
+ * distinct keys.  The session holds nothing the launch writes: calls of one session may be in flight on several streams.
+ */
+int d2pc_sectors_steer_device(d2pc_sectors_steer *s, const d2pc_sectors_steer_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

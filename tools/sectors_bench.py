@@ -38,6 +38,15 @@ ranks them).  GPU box only.
                                             and M of 72 x 1 and 60 x 30 elevation on the rig's merged cloud, the outputs of the two
                                             builds compared bit for bit first, all twelve arms in ONE interleaved run; a row's new
                                             median may exceed the parent's by no more than the arms' spread in that run
+  python tools/sectors_bench.py --steer [--parent NAME]
+                                        ->  profiles/sectors_steer_bench.txt: the steer (d2pc_sectors_steer_device, one launch of one
+                                            block) behind the sectors and the memory: T = the steer alone (T32: 32 candidates), SMT =
+                                            the sectors call + the update + the steer, beside S0, M and SM of the same sessions, on the
+                                            one-camera frame and on the rig's merged cloud, for 72 x 1 and 60 x 30 elevation, in ONE
+                                            interleaved run.  No time is fixed in advance: the yardsticks are S0 and M of the same run.
+                                            With --parent NAME also T and T32 of libd2pc_sectors_NAME.so, another build of the steer's
+                                            kernel (`make sectors SNAME=butterfly SDEFS=-DD2PC_SECTORS_STEER_FORM=0`: the form of the
+                                            candidate rounds that lost), its outputs compared bit for bit with this build's first
 """
 import argparse
 import os
@@ -486,6 +495,135 @@ def memory(a):
     return lines
 
 
+def steer(a):
+    """The steer call beside the sectors call and the memory's update it follows, all arms of all rows interleaved in one run."""
+    import sectors_steer_ref
+    prop = torch.cuda.get_device_properties(0)
+    half_pi = float(np.float32(np.pi / 2))
+    grids = [("72 x 1", dict(), dict(max_reach_sectors=8, max_reach_layers=0)),
+             ("60 x 30 elevation", dict(n_sectors=60, n_layers=30, u_min=-half_pi, u_max=half_pi, azimuth0=-np.pi / 60,
+                                        layer_kind=d2pc.LAYERS_ELEVATION), dict(max_reach_sectors=8, max_reach_layers=4))]
+    lines = ["# tools/sectors_bench.py --steer%s --rounds %d --iters %d" % (" --parent " + a.parent if a.parent else "", a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round)" % (
+                 prop.name, prop.multi_processor_count),
+             "# S0 = d2pc_sectors_process_device with every count 0 (the sectors' fixed part); M = d2pc_sectors_memory_update_device alone;",
+             "# SM = the sectors call then M on one stream (as tools/sectors_bench.py --memory has them); T = d2pc_sectors_steer_device alone",
+             "# (one launch of one block; radius 0.5, reach 8 sectors and 0 / 4 layers, clearance_cm, cost, 5 candidates and summary, from",
+             "# the memory's distance_cm); T32 = the same with 32 candidates; SMT = SM then T on one stream.  us per call: median (min .. max)",
+             "# over the rounds.  No time was fixed in advance: T is read against M and S0 of its row.  CPU = tests/sectors_steer_ref.py",
+             "# (numpy, one core) on the same distance_cm, ms per call"]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    clouds, keep = [], []
+    for name, n, w, h, mode, rig_case, holes in CASES[:2]:
+        with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx:
+            prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+            prod(s)
+            torch.cuda.synchronize()
+            ctx.check_async_error()
+            npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n]) if rig_case else int(prod.counts.cpu().numpy().view(np.uint32)[0])
+            clouds.append((name, npts, prod.pts[:npts].clone()))
+            prod.close()
+    R = np.array([[np.cos(0.6458), 0.0, np.sin(0.6458)], [0.0, 1.0, 0.0], [-np.sin(0.6458), 0.0, np.cos(0.6458)]])   # about the optical y
+    step = torch.from_numpy(d2pc.sectors_memory_step(R, [0.4, -0.1, 0.9], 50).view(np.int32).copy()).to("cuda")
+    arms, labels, rows, versus = [], [], [], []
+    for cname, npts, cloud in clouds:
+        zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+        for gname, grid, reach in grids:
+            sec = d2pc.Sectors(**grid)
+            mem = d2pc.SectorsMemory(sec.cfg, 2000)
+            st = d2pc.SectorsSteer(sec.cfg, **reach)
+            goal = torch.from_numpy(d2pc.sectors_steer_step(sec.cfg.n_sectors // 3, sec.cfg.n_layers // 2, 1, sec.cfg.n_layers // 2)
+                                    .view(np.int32).copy()).to("cuda")
+            cov = torch.from_numpy(d2pc.sectors_memory_coverage(sec.cfg, [(0.0, 0.0, 1.5, 1.0, 0.05)])).to("cuda")
+            so = dict(count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                      nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+            so0 = {k: torch.empty_like(v) for k, v in so.items()}   # S0's own: M reads a full cloud's count / nearest from `so`
+            mo = dict(distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
+            to = dict(clearance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"),
+                      cost=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                      candidates=torch.empty(32, dtype=torch.int64, device="cuda"), summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+            keep.append((sec, mem, st, goal, cov, so, so0, mo, to, zero))
+
+            def sectors(sec=sec, cloud=cloud, npts=npts, so=so):
+                sec.process(cloud, npts, stream_ptr=s, **so)
+
+            def empty(sec=sec, cloud=cloud, npts=npts, so0=so0, zero=zero):
+                sec.process(cloud, npts, counts=zero, stream_ptr=s, **so0)
+
+            def update(mem=mem, cloud=cloud, npts=npts, so=so, mo=mo, cov=cov):
+                mem.update(cloud, npts, so["count"], so["nearest"], step, covered=cov, stream_ptr=s, **mo)
+
+            def turn(st=st, mo=mo, to=to, goal=goal, k=5):
+                st.steer(mo["distance_cm"], goal, n_candidates=k, stream_ptr=s, **to)
+
+            def turn32(turn=turn):
+                turn(k=32)
+
+            def both(sectors=sectors, update=update):
+                sectors()
+                update()
+
+            def three(both=both, turn=turn):
+                both()
+                turn()
+
+            row = "%s, %s" % (cname, gname)
+            rows.append((row, npts, sec, st, mo, goal))
+            arms += [empty, update, both, turn, turn32, three]
+            labels += [row + " " + k for k in ("S0", "M", "SM", "T", "T32", "SMT")]
+            if a.parent:   # the other build's steer on the same input, with outputs of its own
+                other = d2pc.SectorsSteer(sec.cfg, variant=a.parent, **reach)
+                oo = {k: torch.empty_like(v) for k, v in to.items()}
+                keep.append((None, None, other, oo))
+                arms += [lambda other=other, mo=mo, oo=oo, goal=goal: other.steer(mo["distance_cm"], goal, n_candidates=5, stream_ptr=s, **oo),
+                         lambda other=other, mo=mo, oo=oo, goal=goal: other.steer(mo["distance_cm"], goal, n_candidates=32, stream_ptr=s, **oo)]
+                labels += [row + " T " + a.parent, row + " T32 " + a.parent]
+                versus.append((row, to, oo, turn32, arms[-1]))
+    for _ in range(3):   # warm-up: code objects; three updates, so that the memories hold what left the field of view
+        for fn in arms:
+            fn()
+    torch.cuda.synchronize()
+    for row, to, oo, mine, theirs in versus:   # 32 candidates of both builds from the same distance_cm
+        mine()
+        theirs()
+        torch.cuda.synchronize()
+        assert all(torch.equal(to[k], oo[k]) for k in to), row + ": the builds disagree"
+    iters = int(min(max(a.iters, 30000.0 / timed(arms[2], 5)), 4000))
+    t = dict(zip(labels, interleaved(arms, a.rounds, iters)))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    lines.append("# %d calls per timed window" % iters)
+    lines.append("%-62s %10s %6s %6s %-30s %-30s %-30s %-30s %-30s %-30s %6s %6s %8s %7s" % (
+        "cloud, grid", "points", "cells", "free", "S0", "M", "SM", "T", "T32", "SMT", "T/M", "T/S0", "SMT-SM", "CPU ms"))
+    for row, npts, sec, st, mo, goal in rows:
+        torch.cuda.synchronize()
+        dcm = mo["distance_cm"].cpu().numpy().view(np.uint16)
+        ref = sectors_steer_ref.SectorsSteerRef(sec.cfg, st.scfg, *d2pc.sectors_steer_reach(sec.cfg, st.scfg))
+        t0 = time.perf_counter()
+        want = ref.steer(dcm, goal.cpu().numpy().view(np.uint32), None, 5)
+        cpu = (time.perf_counter() - t0) * 1e3
+        lines.append("%-62s %10d %6d %6d %-30s %-30s %-30s %-30s %-30s %-30s %6.2f %6.2f %8.1f %7.2f" % (
+            row, npts, sec.n_cells, int(want["summary"][0]), fmt(t[row + " S0"]), fmt(t[row + " M"]), fmt(t[row + " SM"]), fmt(t[row + " T"]),
+            fmt(t[row + " T32"]), fmt(t[row + " SMT"]), med[row + " T"] / med[row + " M"], med[row + " T"] / med[row + " S0"],
+            med[row + " SMT"] - med[row + " SM"], cpu))
+    if a.parent:
+        lines.append("# the steer of libd2pc_sectors_%s.so (`make sectors SNAME=%s SDEFS=...`) on the same input in the same run; the two builds'" % (a.parent, a.parent))
+        lines.append("# outputs (32 candidates) were compared bit for bit before the timing")
+        lines.append("%-62s %-30s %-30s %-30s %-30s %8s %8s" % ("cloud, grid", "T", "T " + a.parent, "T32", "T32 " + a.parent, "T ratio", "T32 ratio"))
+        for row, *_ in rows:
+            lines.append("%-62s %-30s %-30s %-30s %-30s %8.2f %8.2f" % (
+                row, fmt(t[row + " T"]), fmt(t[row + " T " + a.parent]), fmt(t[row + " T32"]), fmt(t[row + " T32 " + a.parent]),
+                med[row + " T " + a.parent] / med[row + " T"], med[row + " T32 " + a.parent] / med[row + " T32"]))
+    for sec, mem, st, *_ in keep:
+        st.close()
+        if mem is not None:
+            mem.close()
+            sec.close()
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -494,15 +632,16 @@ def main():
     ap.add_argument("--ab", action="store_true", help="the A/B of the in-wave reduction instead of the cost table")
     ap.add_argument("--elevation", action="store_true", help="elevation layers beside height layers instead of the cost table")
     ap.add_argument("--memory", action="store_true", help="the memory's update beside the sectors call instead of the cost table")
+    ap.add_argument("--steer", action="store_true", help="the steer call beside the sectors call and the memory's update instead of the cost table")
     ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
                     "alone, the table of this build against it (S of four grids, M of two)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.parent and (a.memory or a.ab):
-        ap.error("--parent goes with --elevation or stands alone (its own table holds the memory's rows)")
-    versus = bool(a.parent) and not (a.memory or a.elevation or a.ab)
-    out = a.out or os.path.join(ROOT, "profiles", "sectors_memory_bench.txt" if a.memory else "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_refactor_bench.txt" if versus else "sectors_bench.txt")
-    lines = memory(a) if a.memory else elevation(a) if a.elevation else ab(a) if a.ab else parent(a) if versus else bench(a)
+        ap.error("--parent goes with --elevation or --steer or stands alone (its own table holds the memory's rows)")
+    versus = bool(a.parent) and not (a.memory or a.elevation or a.ab or a.steer)
+    out = a.out or os.path.join(ROOT, "profiles", "sectors_steer_bench.txt" if a.steer else "sectors_memory_bench.txt" if a.memory else "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_refactor_bench.txt" if versus else "sectors_bench.txt")
+    lines = steer(a) if a.steer else memory(a) if a.memory else elevation(a) if a.elevation else ab(a) if a.ab else parent(a) if versus else bench(a)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         f.write("\n".join(lines) + "\n")

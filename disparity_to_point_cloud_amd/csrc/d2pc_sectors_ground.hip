@@ -1,0 +1,391 @@
+// d2pc_sectors_ground.hip -- the three kernels of the ground session of include/d2pc_sectors.h (gfx950).
+//
+// k_ground_reduce    min(the session's blocks, the call's shares) blocks of 256 lanes; block b walks shares b, b + blocks, ...
+//                    of the call's records as k_sectors_reduce does (a share is 1,024 records of one cloud, four 16-byte
+//                    loads in flight per lane; a 32-byte record is the load of its first half).  About a dozen VALU
+//                    operations bin a record, so the LDS atomics are what it costs.  Each block keeps a private table of
+//                    the cells in dynamic LDS: sum (64-bit), sum2 (64-bit), count, 20 bytes per cell, and every lane issues
+//                    its own three LDS adds (the 64-bit add is native).  The other form is built behind one macro: a nadir
+//                    camera's row-major cloud puts the 64 neighbouring records of a wave into one or two cells, so a wave can
+//                    first reduce inside itself -- the cell of the first live lane is elected, the lanes that match it add up
+//                    their k (one 32-bit DPP sum) and their k * k (two DPP sums of 16-bit halves: 64 squares of up to 2^30
+//                    do not fit 32 bits) and ONE lane issues the three LDS adds; two such rounds, then per-lane adds for
+//                    the lanes still live.  Measured (profiles/sectors_ground_bench.txt), the per-lane form
+//                    wins in seven rows of eight, for 16 x 16 and for 64 x 64 cells, in producer order and shuffled (the rig's
+//                    merged cloud at 16 x 16 in producer order is the eighth, by 7 %): three DPP sums of six steps
+//                    each and two ballots a round cost more than the serialised adds they save.  So kGroundWaveRounds is 0
+//                    for every grid, at compile time: the product's kernel holds nothing of the rounds;
+//                    -DD2PC_SECTORS_GROUND_FORCE_ROUNDS=0 / =2 build the two arms (tools/sectors_bench.py --ground).
+//                    At the end the block stores its table to its own slab with plain vector stores: no global atomic,
+//                    nothing to clear, no protocol between blocks.
+// k_ground_merge     sums over the slabs of the blocks that ran, 16 cells x 16 slices of the slabs per block (a row of 16
+//                    cells is a whole 128-byte line of the 64-bit sums), a tree through LDS over the slices, then the six
+//                    per-cell outputs the caller asked for and the 13 bytes per cell the sites read.
+// k_ground_sites     ONE block of 1,024 lanes, four cells a lane at the most: mean_q and flat into LDS, the direct
+//                    (2W + 1)^2 walk, cost and key in registers, the K smallest keys with the steer's rounds (DPP minima of
+//                    cost then cell, one 64-bit LDS min into the round's own word, one barrier a round), the summary from
+//                    wave reductions.  It reads what the merge wrote behind a kernel boundary: no global atomic.
+// Every accumulated value is an integer: the result is the same bytes whatever order lanes, waves and blocks arrive in.
+// Every float expression of the specification is rounded once: contraction is off in this file.
+#include <hip/hip_runtime.h>
+
+#include "d2pc_sectors_ground_plan.hpp"
+
+namespace d2pc {
+namespace sectors {
+namespace {
+
+// elected cells per wave and record slot: none in the product, as measured.  A compile-time constant: the product's kernel
+// holds no code of the rounds
+#ifdef D2PC_SECTORS_GROUND_FORCE_ROUNDS
+constexpr int kGroundWaveRounds = D2PC_SECTORS_GROUND_FORCE_ROUNDS;
+#else
+constexpr int kGroundWaveRounds = 0;
+#endif
+constexpr uint32_t kNoCell = 0xFFFFFFFFu;
+constexpr unsigned long long kNoKey = ~0ull;
+
+struct GroundArgs {   // GroundLaunch without its host-only members
+  const uint4 *points;
+  const uint32_t *counts;
+  const float *step;
+  const uint8_t *allowed;
+  unsigned long long *slabs;
+  uint32_t *hand_on;
+  uint32_t *count;
+  unsigned long long *sum, *sum2;
+  uint32_t *mean_q, *spread_q2;
+  uint8_t *flat, *site;
+  unsigned long long *candidates;
+  uint32_t *summary;
+  uint64_t stride, shares;
+  uint32_t shares_per_cloud, cloud_points, n_clouds, step16;
+  int blocks, n_candidates;
+  int n_a, n_b, n_cells, window;
+  int axis_a, axis_b, axis_h;
+  uint32_t flip_a, flip_b, flip_h;
+  float inv_c, inv_q;
+  uint32_t min_count, max_spread_q2, max_step_q, w_dist, w_rough, rough_cap;
+};
+
+// the block's slab: sum and sum2 as 64-bit words of n_cells each, then the counts
+__device__ __forceinline__ unsigned long long *slab_of(const GroundArgs &a, int block) {
+  return a.slabs + size_t(block) * (2u * size_t(a.n_cells) + (size_t(a.n_cells) + 1u) / 2u);   // (GroundPlan::block_bytes, in 64-bit words)
+}
+
+// the sum over the wave's 64 lanes, in every lane; all 64 lanes are active at every call (the callers' control flow is
+// uniform).  row_shr 1, 2, 4, 8 scan a row of 16 (a lane with no source adds 0); row_bcast:15 / :31 carry the rows' totals
+// on: lane 63 holds all
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#define D2PC_GROUND_DPP_ADD(ctrl, rows) v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), ctrl, rows, 0xf, false))
+  D2PC_GROUND_DPP_ADD(0x111, 0xf);
+  D2PC_GROUND_DPP_ADD(0x112, 0xf);
+  D2PC_GROUND_DPP_ADD(0x114, 0xf);
+  D2PC_GROUND_DPP_ADD(0x118, 0xf);
+  D2PC_GROUND_DPP_ADD(0x142, 0xa);
+  D2PC_GROUND_DPP_ADD(0x143, 0xc);
+#undef D2PC_GROUND_DPP_ADD
+  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
+}
+
+// the wave's minimum of a 32-bit word in every lane (d2pc_sectors_steer.hip's, copied: the kernels share no code)
+__device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
+#define D2PC_GROUND_DPP_MIN(ctrl, rows)                                                             \
+  {                                                                                                 \
+    const uint32_t o = uint32_t(__builtin_amdgcn_update_dpp(-1, int(v), ctrl, rows, 0xf, false));   \
+    v = o < v ? o : v;                                                                              \
+  }
+  D2PC_GROUND_DPP_MIN(0x111, 0xf)
+  D2PC_GROUND_DPP_MIN(0x112, 0xf)
+  D2PC_GROUND_DPP_MIN(0x114, 0xf)
+  D2PC_GROUND_DPP_MIN(0x118, 0xf)
+  D2PC_GROUND_DPP_MIN(0x142, 0xa)
+  D2PC_GROUND_DPP_MIN(0x143, 0xc)
+#undef D2PC_GROUND_DPP_MIN
+  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
+}
+
+// one record slot of the wave into the block's table; k is the height in quanta, |k| <= 32767
+__device__ __forceinline__ void merge(unsigned long long *sum, unsigned long long *sum2, uint32_t *cnt, uint32_t cell, int k) {
+  bool live = cell != kNoCell;
+  [[maybe_unused]] const uint32_t lane = __lane_id();
+  const uint32_t k2 = uint32_t(k * k);   // < 2^30
+#pragma unroll
+  for (int round = 0; round < kGroundWaveRounds; ++round) {
+    const unsigned long long any = __ballot(live);
+    if (any == 0) break;
+    const int leader = __ffsll(any) - 1;
+    const uint32_t elected = uint32_t(__builtin_amdgcn_readlane(int(cell), leader));
+    const bool mine = live && cell == elected;
+    const uint32_t n = uint32_t(__popcll(__ballot(mine)));
+    const int s = int(wave_sum(mine ? uint32_t(k) : 0u));            // |the sum| <= 64 x 32767
+    const uint32_t lo = wave_sum(mine ? k2 & 0xFFFFu : 0u);          // <= 64 x 65535
+    const uint32_t hi = wave_sum(mine ? k2 >> 16 : 0u);              // <= 64 x 2^14
+    if (lane == uint32_t(leader)) {
+      atomicAdd(&sum[elected], static_cast<unsigned long long>(static_cast<long long>(s)));
+      atomicAdd(&sum2[elected], (static_cast<unsigned long long>(hi) << 16) + lo);
+      atomicAdd(&cnt[elected], n);
+    }
+    live = live && !mine;
+  }
+  if (live) {
+    atomicAdd(&sum[cell], static_cast<unsigned long long>(static_cast<long long>(k)));
+    atomicAdd(&sum2[cell], static_cast<unsigned long long>(k2));
+    atomicAdd(&cnt[cell], 1u);
+  }
+}
+
+__device__ __forceinline__ float pick(int axis, uint32_t flip, float x, float y, float z) {
+  const float v = axis == 0 ? x : (axis == 1 ? y : z);
+  return __uint_as_float(__float_as_uint(v) ^ flip);   // (a negation is exact)
+}
+
+__global__ __launch_bounds__(kThreads) void k_ground_reduce(const GroundArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ __align__(16) unsigned char lds[];
+  unsigned long long *sum = reinterpret_cast<unsigned long long *>(lds);
+  unsigned long long *sum2 = sum + a.n_cells;
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(sum2 + a.n_cells);
+  const uint32_t tid = threadIdx.x;
+  for (int i = int(tid); i < a.n_cells; i += kThreads) sum[i] = 0ull, sum2[i] = 0ull, cnt[i] = 0u;
+  // the step: the same 15 words in every lane
+  const float r0 = a.step[0], r1 = a.step[1], r2 = a.step[2], r3 = a.step[3], r4 = a.step[4], r5 = a.step[5], r6 = a.step[6],
+              r7 = a.step[7], r8 = a.step[8], tx = a.step[9], ty = a.step[10], tz = a.step[11], a0 = a.step[12], b0 = a.step[13],
+              h0 = a.step[14];
+  const float na = float(a.n_a), nb = float(a.n_b);
+  __syncthreads();
+
+  for (uint64_t share = blockIdx.x; share < a.shares; share += uint64_t(a.blocks)) {
+    uint64_t cloud = 0;
+    uint32_t in_cloud = uint32_t(share);
+    if (a.n_clouds > 1) {
+      cloud = share / a.shares_per_cloud;
+      in_cloud = uint32_t(share - cloud * a.shares_per_cloud);
+    }
+    uint32_t n = a.cloud_points;
+    if (a.counts) {
+      const uint32_t given = a.counts[cloud];
+      n = given == 0xFFFFFFFFu ? 0u : min(given, a.cloud_points);
+    }
+    const uint32_t i0 = in_cloud * uint32_t(D2PC_SECTORS_SHARE_POINTS);   // (< 2^32: shares_per_cloud <= 2^22)
+    if (i0 >= n) continue;
+    const uint64_t first = cloud * a.stride;   // the cloud's first record in `points`
+    uint4 rec[kPerLane];
+    bool have[kPerLane];
+#pragma unroll
+    for (int k = 0; k < kPerLane; ++k) {
+      const uint32_t i = i0 + uint32_t(k * kThreads) + tid;   // (i0 + 1,023 <= 2^32 - 1: no wrap)
+      have[k] = i < n;
+      rec[k] = make_uint4(0u, 0u, 0u, 0u);
+      if (have[k]) rec[k] = a.points[(first + i) * a.step16];
+      asm volatile("" ::"v"(rec[k].w));   // keeps the load a whole 16-byte one (w is not used: it would shrink to 12)
+    }
+    uint32_t cell[kPerLane];
+    int q[kPerLane];
+#pragma unroll
+    for (int k = 0; k < kPerLane; ++k) {
+      const bool finite = (rec[k].x & 0x7F800000u) != 0x7F800000u && (rec[k].y & 0x7F800000u) != 0x7F800000u &&
+                          (rec[k].z & 0x7F800000u) != 0x7F800000u;
+      const float x = __uint_as_float(rec[k].x), y = __uint_as_float(rec[k].y), z = __uint_as_float(rec[k].z);
+      const float wx = ((r0 * x + r1 * y) + r2 * z) + tx;
+      const float wy = ((r3 * x + r4 * y) + r5 * z) + ty;
+      const float wz = ((r6 * x + r7 * y) + r8 * z) + tz;
+      const float pa = pick(a.axis_a, a.flip_a, wx, wy, wz), pb = pick(a.axis_b, a.flip_b, wx, wy, wz);
+      const float ph = pick(a.axis_h, a.flip_h, wx, wy, wz);
+      const float va = (pa - a0) * a.inv_c, vb = (pb - b0) * a.inv_c, v = (ph - h0) * a.inv_q;
+      const bool part = have[k] && finite && va >= 0.0f && va < na && vb >= 0.0f && vb < nb && v >= -32767.0f && v <= 32767.0f;
+      const int ia = int(floorf(va)), ib = int(floorf(vb));
+      cell[k] = part ? uint32_t(ib * a.n_a + ia) : kNoCell;
+      q[k] = part ? int(rintf(v)) : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < kPerLane; ++k) merge(sum, sum2, cnt, cell[k], q[k]);
+  }
+
+  __syncthreads();
+  unsigned long long *slab = slab_of(a, int(blockIdx.x));
+  uint32_t *slab_c = reinterpret_cast<uint32_t *>(slab + 2 * size_t(a.n_cells));
+  for (int i = int(tid); i < a.n_cells; i += kThreads) slab[i] = sum[i], slab[a.n_cells + i] = sum2[i], slab_c[i] = cnt[i];
+}
+
+__global__ __launch_bounds__(kThreads) void k_ground_merge(const GroundArgs a) {
+  __shared__ unsigned long long s1[kThreads], s2[kThreads];
+  __shared__ uint32_t sc[kThreads];
+  const int tid = int(threadIdx.x), slice = tid / kGroundMergeCells;
+  const int cell = int(blockIdx.x) * kGroundMergeCells + tid % kGroundMergeCells;
+  const int n_cells = a.n_cells;
+  unsigned long long sum = 0, sum2 = 0;
+  uint32_t cnt = 0;
+  if (cell < n_cells) {
+#pragma unroll 4
+    for (int b = slice; b < a.blocks; b += kGroundMergeSlices) {
+      const unsigned long long *slab = slab_of(a, b);
+      sum += slab[cell], sum2 += slab[n_cells + cell];
+      cnt += reinterpret_cast<const uint32_t *>(slab + 2 * size_t(n_cells))[cell];
+    }
+  }
+  s1[tid] = sum, s2[tid] = sum2, sc[tid] = cnt;
+  for (int s = kGroundMergeSlices / 2; s >= 1; s >>= 1) {
+    __syncthreads();
+    if (slice < s) {
+      sum += s1[tid + s * kGroundMergeCells], sum2 += s2[tid + s * kGroundMergeCells], cnt += sc[tid + s * kGroundMergeCells];
+      s1[tid] = sum, s2[tid] = sum2, sc[tid] = cnt;
+    }
+  }
+  if (slice != 0 || cell >= n_cells) return;
+  uint32_t mean = D2PC_SECTORS_GROUND_EMPTY_MEAN, spread = D2PC_SECTORS_GROUND_EMPTY_SPREAD;
+  if (cnt != 0u) {
+    const long long total = static_cast<long long>(sum), c = static_cast<long long>(cnt);
+    long long m = total / c;
+    m -= (total % c != 0 && total < 0) ? 1 : 0;   // floor division towards -inf
+    const unsigned long long um = static_cast<unsigned long long>(m);
+    const unsigned long long S = sum2 - 2ull * um * sum + static_cast<unsigned long long>(cnt) * um * um;   // wrapping: exact
+    mean = uint32_t(int(m)), spread = uint32_t(S / static_cast<unsigned long long>(cnt));
+  }
+  const uint8_t flat = cnt >= a.min_count && spread <= a.max_spread_q2 ? 1 : 0;   // (min_count >= 1: an empty cell is never flat)
+  if (a.count) a.count[cell] = cnt;
+  if (a.sum) a.sum[cell] = sum;
+  if (a.sum2) a.sum2[cell] = sum2;
+  if (a.mean_q) a.mean_q[cell] = mean;
+  if (a.spread_q2) a.spread_q2[cell] = spread;
+  if (a.flat) a.flat[cell] = flat;
+  a.hand_on[cell] = cnt, a.hand_on[n_cells + cell] = mean, a.hand_on[2 * n_cells + cell] = spread;
+  reinterpret_cast<uint8_t *>(a.hand_on + 3 * size_t(n_cells))[cell] = flat;
+}
+
+__global__ __launch_bounds__(kGroundSiteThreads) void k_ground_sites(const GroundArgs a) {
+  __shared__ int mean_s[kGroundMaxCells];
+  __shared__ uint8_t flat_s[kGroundMaxCells];
+  __shared__ unsigned long long winner[D2PC_SECTORS_GROUND_MAX_CANDIDATES];   // round r's own word
+  __shared__ uint32_t slot[3][kGroundSiteWaves];
+  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+  const int n_cells = a.n_cells, n_a = a.n_a, n_b = a.n_b, W = a.window;
+  if (tid < D2PC_SECTORS_GROUND_MAX_CANDIDATES) winner[tid] = kNoKey;   // (a barrier lies before the first min into it)
+  const uint8_t *flat_g = reinterpret_cast<const uint8_t *>(a.hand_on + 3 * size_t(n_cells));
+  uint32_t points = 0, n_flat = 0, n_sites = 0;
+  uint32_t spread[kGroundPerLane] = {};
+#pragma unroll
+  for (int k = 0; k < kGroundPerLane; ++k) {
+    const int c = tid + k * kGroundSiteThreads;
+    if (c >= n_cells) continue;
+    const uint8_t f = flat_g[c];
+    points += a.hand_on[c], n_flat += f;
+    mean_s[c] = int(a.hand_on[n_cells + c]), flat_s[c] = f;
+    spread[k] = a.hand_on[2 * n_cells + c];
+  }
+  const uint32_t goal_i = reinterpret_cast<const uint32_t *>(a.step)[15], goal_j = reinterpret_cast<const uint32_t *>(a.step)[16];
+  const bool measured = goal_i < uint32_t(n_a) && goal_j < uint32_t(n_b);
+  __syncthreads();
+
+  unsigned long long key[kGroundPerLane];
+#pragma unroll
+  for (int k = 0; k < kGroundPerLane; ++k) {
+    key[k] = kNoKey;
+    const int c = tid + k * kGroundSiteThreads;
+    if (c >= n_cells) continue;
+    const int j = c / n_a, i = c - j * n_a;
+    bool site = i - W >= 0 && i + W < n_a && j - W >= 0 && j + W < n_b && flat_s[c] != 0 && (!a.allowed || a.allowed[c] != 0);
+    if (site) {
+      const int m = mean_s[c], step = int(a.max_step_q);
+      for (int dj = -W; dj <= W; ++dj)
+        for (int di = -W; di <= W; ++di) {
+          const int o = c + dj * n_a + di;
+          if (flat_s[o] == 0) site = false;   // (an empty cell's mean is 0x80000000: no difference is formed with it)
+          if (site) {
+            const int d = mean_s[o] - m;   // of flat cells: |mean_q| <= 32767
+            site = (d < 0 ? -d : d) <= step;
+          }
+        }
+    }
+    if (a.site) a.site[c] = site ? 1 : 0;
+    if (site) {
+      const int di = i - int(goal_i), dj = j - int(goal_j);
+      const uint32_t dist = measured ? uint32_t(di * di + dj * dj) : 0u;
+      const uint32_t cost = a.w_dist * dist + a.w_rough * (spread[k] < a.rough_cap ? spread[k] : a.rough_cap);
+      key[k] = (static_cast<unsigned long long>(cost) << 32) | uint32_t(c);
+      ++n_sites;
+    }
+  }
+
+  // ---- the summary
+  if (a.summary) {   // (uniform: a kernel argument)
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      points += uint32_t(__shfl_xor(int(points), m, 64));
+      n_flat += uint32_t(__shfl_xor(int(n_flat), m, 64));
+      n_sites += uint32_t(__shfl_xor(int(n_sites), m, 64));
+    }
+    if (lane == 0) slot[0][wave] = points, slot[1][wave] = n_flat, slot[2][wave] = n_sites;
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t t0 = 0, t1 = 0, t2 = 0;
+      for (int w = 0; w < kGroundSiteWaves; ++w) t0 += slot[0][w], t1 += slot[1][w], t2 += slot[2][w];
+      a.summary[0] = t0, a.summary[1] = t1, a.summary[2] = t2, a.summary[3] = 0u;
+    }
+  }
+
+  // ---- the K smallest keys, ascending (the steer's rounds)
+  unsigned long long head = key[0];   // the lane's smallest key not yet chosen
+#pragma unroll
+  for (int k = 1; k < kGroundPerLane; ++k) head = key[k] < head ? key[k] : head;
+  for (int r = 0; r < a.n_candidates; ++r) {
+    const uint32_t head_cost = uint32_t(head >> 32), head_cell = uint32_t(head);   // (all ones for no key: no cost is)
+    const uint32_t least = wave_umin(head_cost);
+    const uint32_t cell = wave_umin(head_cost == least ? head_cell : 0xFFFFFFFFu);
+    if (lane == 0 && least != 0xFFFFFFFFu) atomicMin(&winner[r], (static_cast<unsigned long long>(least) << 32) | cell);
+    __syncthreads();
+    const unsigned long long best = winner[r];   // (the same value in every lane)
+    if (best == kNoKey) {   // no site is left: all ones from here on
+      if (tid < a.n_candidates - r) a.candidates[r + tid] = kNoKey;
+      break;
+    }
+    if (tid == 0) a.candidates[r] = best;
+    if (head == best) {   // one lane of the block: its next key
+      head = kNoKey;
+#pragma unroll
+      for (int k = 0; k < kGroundPerLane; ++k) head = key[k] > best && key[k] < head ? key[k] : head;
+    }
+  }
+}
+
+}  // namespace
+
+int prepare_ground_kernels(const GroundPlan &p) {
+  // beyond 64 KB of dynamic LDS the runtime wants to be told (64 x 64 cells need 81,920 bytes)
+  if (p.lds_bytes <= 64u * 1024u) return int(hipSuccess);
+  return int(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ground_reduce), hipFuncAttributeMaxDynamicSharedMemorySize, int(p.lds_bytes)));
+}
+
+int launch_ground(const GroundLaunch &in) {
+  GroundArgs a;
+  a.points = static_cast<const uint4 *>(in.points), a.counts = in.counts, a.step = static_cast<const float *>(in.step);
+  a.allowed = in.allowed;
+  a.slabs = static_cast<unsigned long long *>(in.slabs), a.hand_on = static_cast<uint32_t *>(in.hand_on);
+  a.count = in.count, a.sum = reinterpret_cast<unsigned long long *>(in.sum), a.sum2 = reinterpret_cast<unsigned long long *>(in.sum2);
+  a.mean_q = reinterpret_cast<uint32_t *>(in.mean_q), a.spread_q2 = in.spread_q2, a.flat = in.flat, a.site = in.site;
+  a.candidates = static_cast<unsigned long long *>(in.candidates), a.summary = in.summary;
+  a.n_candidates = in.candidates ? in.n_candidates : 0;
+  a.stride = in.stride, a.shares = in.shares;
+  a.shares_per_cloud = in.shares_per_cloud, a.cloud_points = in.cloud_points, a.n_clouds = in.n_clouds, a.step16 = in.step16;
+  a.blocks = in.blocks;
+  const GroundPlan &p = in.plan;
+  a.n_a = p.n_a, a.n_b = p.n_b, a.n_cells = p.n_cells, a.window = p.window;
+  a.axis_a = p.axis[0], a.axis_b = p.axis[1], a.axis_h = p.axis[2];
+  a.flip_a = p.flip[0], a.flip_b = p.flip[1], a.flip_h = p.flip[2];
+  a.inv_c = p.inv_c, a.inv_q = p.inv_q;
+  a.min_count = p.min_count, a.max_spread_q2 = p.max_spread_q2, a.max_step_q = p.max_step_q;
+  a.w_dist = p.w_dist, a.w_rough = p.w_rough, a.rough_cap = p.rough_cap;
+  hipStream_t s = static_cast<hipStream_t>(in.stream);
+  void *args[] = {&a};
+  (void)hipLaunchKernel(reinterpret_cast<const void *>(&k_ground_reduce), dim3(unsigned(in.blocks)), dim3(kThreads), args, p.lds_bytes, s);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return int(e);
+  hipLaunchKernelGGL(k_ground_merge, dim3(unsigned((p.n_cells + kGroundMergeCells - 1) / kGroundMergeCells)), dim3(kThreads), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess || !(in.site || in.candidates || in.summary)) return int(e);
+  hipLaunchKernelGGL(k_ground_sites, dim3(1), dim3(kGroundSiteThreads), 0, s, a);
+  return int(hipGetLastError());
+}
+
+}  // namespace sectors
+}  // namespace d2pc

@@ -28,12 +28,19 @@ SECTORS_SYMBOLS = [
     "d2pc_sectors_steer_config_init", "d2pc_sectors_steer_reach", "d2pc_sectors_steer_goal_cell", "d2pc_sectors_steer_create",
     "d2pc_sectors_steer_destroy", "d2pc_sectors_steer_last_error", "d2pc_sectors_steer_desc_init", "d2pc_sectors_steer_desc_check",
     "d2pc_sectors_steer_device",
+    "d2pc_sectors_ground_config_init", "d2pc_sectors_ground_geometry", "d2pc_sectors_ground_spread_of_std", "d2pc_sectors_ground_create",
+    "d2pc_sectors_ground_destroy", "d2pc_sectors_ground_last_error", "d2pc_sectors_ground_blocks", "d2pc_sectors_ground_desc_init",
+    "d2pc_sectors_ground_desc_check", "d2pc_sectors_ground_process_device",
 ]
 EMPTY_AGE, OLDEST_AGE = 0xFFFFFFFF, 0xFFFFFFFE   # the age word of an empty record; where an age saturates
 STEER_MAX_REACH_SECTORS, STEER_MAX_REACH_LAYERS, STEER_MAX_CANDIDATES, STEER_MAX_WEIGHT = 32, 16, 32, 4095
 STEER_OFF = 0xFFFFFFFF            # a goal_sector / prev_sector that switches its term off
 STEER_NO_CANDIDATE = 0xFFFFFFFFFFFFFFFF   # a candidate slot beyond the free cells
 STEER_BLOCKED = 0xFFFFFFFF        # the cost of a cell that is not free
+GROUND_MAX_CELLS_PER_AXIS, GROUND_MAX_WINDOW, GROUND_MAX_CANDIDATES, GROUND_MAX_WEIGHT, GROUND_MAX_K = 64, 8, 32, 4095, 32767
+GROUND_EMPTY_MEAN, GROUND_EMPTY_SPREAD = 0x80000000, 0xFFFFFFFF   # mean_q (as a uint32) and spread_q2 of an empty cell
+GROUND_OFF = 0xFFFFFFFF           # a goal_i / goal_j that switches the distance term off
+GROUND_NO_CANDIDATE = 0xFFFFFFFFFFFFFFFF  # a candidate slot beyond the sites
 
 
 class SectorsConfig(ctypes.Structure):
@@ -112,6 +119,39 @@ class SectorsSteerDesc(ctypes.Structure):
     ]
 
 
+class SectorsGroundConfig(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("device_id", ctypes.c_int32), ("n_a", ctypes.c_int32), ("n_b", ctypes.c_int32),
+        ("cell_size", ctypes.c_float), ("quantum", ctypes.c_float), ("axes", ctypes.c_int32 * 3), ("min_count", ctypes.c_uint32),
+        ("max_spread_q2", ctypes.c_uint32), ("max_step_q", ctypes.c_uint32), ("window", ctypes.c_int32), ("w_dist", ctypes.c_uint32),
+        ("w_rough", ctypes.c_uint32), ("rough_cap", ctypes.c_uint32), ("max_points", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3),
+    ]
+
+
+class SectorsGroundGeometry(ctypes.Structure):
+    _fields_ = [
+        ("n_cells", ctypes.c_int32), ("inv_c", ctypes.c_float), ("inv_q", ctypes.c_float), ("share_points", ctypes.c_int32),
+        ("blocks_per_cu", ctypes.c_int32), ("blocks", ctypes.c_int32), ("lds_bytes", ctypes.c_size_t), ("block_bytes", ctypes.c_size_t),
+        ("device_bytes", ctypes.c_size_t), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+class SectorsGroundStep(ctypes.Structure):   # 80 bytes, in device memory
+    _fields_ = [("R", ctypes.c_float * 9), ("t", ctypes.c_float * 3), ("origin", ctypes.c_float * 3), ("goal_i", ctypes.c_uint32),
+                ("goal_j", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class SectorsGroundDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("point_step", ctypes.c_int32), ("n_clouds", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
+        ("points", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("cloud_points", ctypes.c_size_t),
+        ("points_frame_stride_points", ctypes.c_size_t), ("step", ctypes.c_void_p), ("allowed", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("sum", ctypes.c_void_p), ("sum2", ctypes.c_void_p), ("mean_q", ctypes.c_void_p),
+        ("spread_q2", ctypes.c_void_p), ("flat", ctypes.c_void_p), ("site", ctypes.c_void_p), ("candidates", ctypes.c_void_p),
+        ("summary", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -180,6 +220,22 @@ def load_sectors_library(variant=None):
         L.d2pc_sectors_steer_desc_init.restype = None
         L.d2pc_sectors_steer_desc_check.argtypes = [cfg, scfg, sdesc]
         L.d2pc_sectors_steer_device.argtypes = [vp, sdesc, vp]
+    if variant is None or hasattr(L, "d2pc_sectors_ground_create"):   # (an A/B variant may be a build from before the ground)
+        gcfg, gdesc = ctypes.POINTER(SectorsGroundConfig), ctypes.POINTER(SectorsGroundDesc)
+        L.d2pc_sectors_ground_config_init.argtypes = [gcfg]
+        L.d2pc_sectors_ground_config_init.restype = None
+        L.d2pc_sectors_ground_geometry.argtypes = [gcfg, ctypes.POINTER(SectorsGroundGeometry)]
+        L.d2pc_sectors_ground_spread_of_std.argtypes = [ctypes.c_double, ctypes.c_double]
+        L.d2pc_sectors_ground_spread_of_std.restype = ctypes.c_uint32
+        L.d2pc_sectors_ground_create.argtypes = [gcfg, ctypes.POINTER(vp)]
+        L.d2pc_sectors_ground_destroy.argtypes = [vp]
+        L.d2pc_sectors_ground_last_error.argtypes = [vp]
+        L.d2pc_sectors_ground_last_error.restype = ctypes.c_char_p
+        L.d2pc_sectors_ground_blocks.argtypes = [vp]
+        L.d2pc_sectors_ground_desc_init.argtypes = [gdesc]
+        L.d2pc_sectors_ground_desc_init.restype = None
+        L.d2pc_sectors_ground_desc_check.argtypes = [gcfg, gdesc]
+        L.d2pc_sectors_ground_process_device.argtypes = [vp, gdesc, vp]
     if variant is None:
         _lib = L
     return L
@@ -459,3 +515,76 @@ class SectorsSteer(_Session):
         self.steer_desc(sectors_steer_desc_init(
             n_candidates=n_candidates, distance_cm=_ptr(distance_cm), allowed=_ptr(allowed), step=_ptr(step),
             clearance_cm=_ptr(clearance_cm), cost=_ptr(cost), candidates=_ptr(candidates), summary=_ptr(summary)), stream_ptr)
+
+
+def sectors_ground_config_init(**kw) -> SectorsGroundConfig:
+    """d2pc_sectors_ground_config_init, then the given fields."""
+    c = SectorsGroundConfig()
+    load_sectors_library().d2pc_sectors_ground_config_init(ctypes.byref(c))
+    return _set(c, kw)
+
+
+def sectors_ground_desc_init(**kw) -> SectorsGroundDesc:
+    """d2pc_sectors_ground_desc_init, then the given fields."""
+    d = SectorsGroundDesc()
+    load_sectors_library().d2pc_sectors_ground_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_ground_geometry(gcfg: SectorsGroundConfig) -> SectorsGroundGeometry:
+    """d2pc_sectors_ground_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = SectorsGroundGeometry()
+    st = load_sectors_library().d2pc_sectors_ground_geometry(ctypes.byref(gcfg), ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "sectors_ground_geometry(%d x %d)" % (gcfg.n_a, gcfg.n_b))
+    return g
+
+
+def sectors_ground_spread_of_std(quantum, std_dev) -> int:
+    """d2pc_sectors_ground_spread_of_std: max_spread_q2 from a standard deviation in the cloud's unit."""
+    return int(load_sectors_library().d2pc_sectors_ground_spread_of_std(quantum, std_dev))
+
+
+def sectors_ground_desc_check(gcfg: SectorsGroundConfig, desc: SectorsGroundDesc) -> int:
+    """d2pc_sectors_ground_desc_check: the status d2pc_sectors_ground_process_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_ground_desc_check(ctypes.byref(gcfg), ctypes.byref(desc))
+
+
+def sectors_ground_step(R, t, origin, goal_i=GROUND_OFF, goal_j=GROUND_OFF) -> np.ndarray:
+    """The 20 words of a d2pc_sectors_ground_step (R row-major, t, origin, the goal cell, three zeros) as uint32, to copy to
+    the device."""
+    w = np.zeros(20, dtype=np.uint32)
+    w[:9] = np.asarray(R, dtype=np.float32).reshape(9).view(np.uint32)
+    w[9:12] = np.asarray(t, dtype=np.float32).reshape(3).view(np.uint32)
+    w[12:15] = np.asarray(origin, dtype=np.float32).reshape(3).view(np.uint32)
+    w[15:17] = np.array([goal_i, goal_j], dtype=np.uint64).astype(np.uint32)
+    return w
+
+
+class SectorsGround(_Session):
+    """d2pc_sectors_ground_*: per-cell ground height statistics in a levelled world frame and ranked landing sites, from any
+    cloud and a pose.  `process` takes torch tensors or raw device pointers, is asynchronous on `stream` and allocates nothing."""
+
+    _PREFIX = "d2pc_sectors_ground"
+
+    def __init__(self, gcfg: SectorsGroundConfig = None, variant=None, **kw):
+        self.cfg = _set(gcfg, kw) if gcfg is not None else sectors_ground_config_init(**kw)
+        self._create(variant, "sectors_ground_create(%d x %d)" % (self.cfg.n_a, self.cfg.n_b), ctypes.byref(self.cfg))
+        self.geometry = sectors_ground_geometry(self.cfg)
+        self.n_cells, self.blocks = self.geometry.n_cells, int(self._L.d2pc_sectors_ground_blocks(self._h))
+
+    def process_desc(self, desc: SectorsGroundDesc, stream_ptr=None):
+        """d2pc_sectors_ground_process_device."""
+        st = self._L.d2pc_sectors_ground_process_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def process(self, points, cloud_points, step, point_step=16, n_clouds=1, counts=None, frame_stride_points=0, allowed=None,
+                count=None, sum=None, sum2=None, mean_q=None, spread_q2=None, flat=None, site=None, candidates=None,
+                n_candidates=1, summary=None, stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.process_desc(sectors_ground_desc_init(
+            point_step=point_step, n_clouds=n_clouds, n_candidates=n_candidates, points=_ptr(points), counts=_ptr(counts),
+            cloud_points=cloud_points, points_frame_stride_points=frame_stride_points, step=_ptr(step), allowed=_ptr(allowed),
+            count=_ptr(count), sum=_ptr(sum), sum2=_ptr(sum2), mean_q=_ptr(mean_q), spread_q2=_ptr(spread_q2), flat=_ptr(flat),
+            site=_ptr(site), candidates=_ptr(candidates), summary=_ptr(summary)), stream_ptr)

@@ -168,6 +168,64 @@
  *                   The list holds the smallest keys among the free cells, ascending: ties in cost go to the smaller
  *                   cell, whatever order the device visits the cells in.  Slots beyond the free cells hold all ones
  *     summary       uint32 x 4: the number of free cells, the smallest d after the free_cm mapping (65535 if none), 0, 0
+ *
+ * ------------------------------------------------------------------------------------- GROUND (d2pc_sectors_ground_*)
+ * What a landing planner asks: "is the ground under me flat enough to land on, and where?".  A Cartesian grid of n_a x n_b
+ * cells in a gravity-levelled world frame; each cell holds the number of its points, the sum of their heights and the sum
+ * of the squares, in integers.  A cell is flat when it has enough points and a small spread; a site is a cell whose whole
+ * neighbourhood is flat and level with it.  d2pc_sectors_ground_process_device makes it from any cloud and a pose, in at
+ * most three launches.  Every accumulated value is an integer: the result is the same bytes whatever order the device
+ * visits the points in.  tests/sectors_ground_ref.py restates it in numpy.
+ *
+ * Step (d2pc_sectors_ground_step, 80 bytes in DEVICE memory, 4-byte aligned):  float R[9], row-major: world = R p + t, as
+ * the memory's step has it;  float t[3];  float origin[3] = a0, b0, h0: a0, b0 are the grid's corner, h0 is the
+ * reference height (the vehicle's altitude, or the last ground estimate);  uint32 goal_i, goal_j;  uint32 reserved[3].
+ * The kernel refuses nothing of a step.
+ *
+ * Per record.
+ *     1. The record's first three floats are x, y, z.  It takes part only if all three are finite.
+ *     2. w.x = fl(fl(fl(fl(R[0]*x) + fl(R[1]*y)) + fl(R[2]*z)) + t.x),  w.y likewise with R[3..5] and t.y,  w.z likewise
+ *        with R[6..8] and t.z: the memory's "fresh" formula, word for word.
+ *     3. axes[3] picks a, b, h from w as the sectors' picks do: +-1, +-2, +-3 of distinct magnitudes.  ENU with z up is
+ *        {1, 2, 3}; NED is {1, 2, -3}.
+ *     4. va = fl(fl(a - a0) * inv_c),  vb = fl(fl(b - b0) * inv_c),  inv_c = (float)(1.0 / (double)cell_size) formed on
+ *        the host.
+ *     5. v = fl(fl(h - h0) * inv_q),  inv_q = (float)(1.0 / (double)quantum).
+ *     6. Gate, exactly so (a NaN passes no comparison):  va >= 0.0f and va < (float)n_a;  vb >= 0.0f and vb < (float)n_b;
+ *        v >= -32767.0f and v <= 32767.0f.  All comparisons are in float, before any conversion.
+ *     7. ia = (int)floorf(va),  ib = (int)floorf(vb),  cell = ib * n_a + ia.
+ *     8. k = (int)rintf(v), round half to even, so |k| <= 32767.
+ *
+ * Cell.  Over the points that take part, from all clouds of the call:  count (uint32);  sum = the sum of k (int64);
+ * sum2 = the sum of k*k (uint64; below 2^62, because a call holds fewer than 2^32 positions).  Sums of integers are the
+ * same bytes in any order.
+ *
+ * Outputs of a cell, n_cells = n_a * n_b entries each, each nullable:
+ *     count      uint32
+ *     sum        int64, 8-byte aligned; the caller may add these across frames, exactly
+ *     sum2       uint64, 8-byte aligned; likewise
+ *     mean_q     int32   m = floor(sum / count), floor division towards -inf, in quanta above h0; 0x80000000 for an
+ *                        empty cell
+ *     spread_q2  uint32  floor(S / count) with S = the sum of (k - m)^2 = sum2 - 2 m sum + count m^2, evaluated in
+ *                        wrapping 64-bit arithmetic (the true S is below 2^64 because |k - m| <= 65534, so the wrapped
+ *                        result is exact; S / count <= 65534^2 < 2^32 - 1 needs no clamp); 0xFFFFFFFF for an empty
+ *                        cell.  The mean squared deviation about the floor mean: within one quantum^2 of the variance
+ *     flat       uint8   1 when count >= min_count and spread_q2 <= max_spread_q2, else 0
+ *
+ * Sites.  W = window, 0 .. 8.  A cell (i, j) = j * n_a + i is a site when every cell (i + di, j + dj) with |di|, |dj| <= W
+ * lies inside the grid, is flat and has |mean_q' - mean_q(i, j)| <= max_step_q, and `allowed` is NULL or allowed[cell]
+ * != 0.  The grid does not wrap: a window that leaves the grid makes no site.  site is uint8 x n_cells.
+ *
+ * Cost of a site, in uint32 (it cannot wrap: weights <= 4095, n <= 64, rough_cap <= 65535):
+ *     cost = w_dist * ((i - goal_i)^2 + (j - goal_j)^2) + w_rough * min(spread_q2, rough_cap)
+ * A goal_i >= n_a or a goal_j >= n_b switches the distance term off.
+ *
+ * Candidates.  n_candidates (at most 32) records {cell, cost}: as a little-endian uint64 a record is (cost << 32) | cell,
+ * the steer's candidate form.  The list holds the smallest keys among the sites, ascending; ties go to the smaller cell.
+ * Slots beyond the sites hold all ones.
+ *
+ * Summary.  uint32 x 4: the points that took part (the sum of count modulo 2^32), the number of flat cells, the number
+ * of sites, 0.
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -436,6 +494,117 @@ int d2pc_sectors_steer_desc_check(const d2pc_sectors_config *grid, const d2pc_se
  * distinct keys.  The session holds nothing the launch writes: calls of one session may be in flight on several streams.
  */
 int d2pc_sectors_steer_device(d2pc_sectors_steer *s, const d2pc_sectors_steer_desc *desc, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------- the ground */
+#define D2PC_SECTORS_GROUND_MAX_CELLS_PER_AXIS 64
+#define D2PC_SECTORS_GROUND_MAX_WINDOW 8
+#define D2PC_SECTORS_GROUND_MAX_CANDIDATES 32
+#define D2PC_SECTORS_GROUND_MAX_WEIGHT 4095
+#define D2PC_SECTORS_GROUND_MAX_K 32767             /* |k| of a point that takes part */
+#define D2PC_SECTORS_GROUND_EMPTY_MEAN 0x80000000u  /* mean_q of an empty cell, as a uint32 */
+#define D2PC_SECTORS_GROUND_EMPTY_SPREAD 0xFFFFFFFFu
+#define D2PC_SECTORS_GROUND_OFF 0xFFFFFFFFu         /* a goal_i / goal_j that switches the distance term off (any value >= n does) */
+
+typedef struct d2pc_sectors_ground_config {   /* fixed for a ground session */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_ground_config) */
+  int32_t device_id;
+  int32_t n_a, n_b;            /* 2 .. 64 each: cells along a and along b */
+  float cell_size;             /* finite and > 0, in the cloud's unit (metres) */
+  float quantum;               /* finite and > 0: the height of one k */
+  int32_t axes[3];             /* a, b, h picked from the WORLD point: +-1, +-2, +-3 of distinct magnitudes */
+  uint32_t min_count;          /* >= 1: a cell with fewer points is not flat */
+  uint32_t max_spread_q2;      /* a cell with a larger spread_q2 is not flat (d2pc_sectors_ground_spread_of_std makes it) */
+  uint32_t max_step_q;         /* <= 65535: the largest |mean_q' - mean_q| inside a site's window */
+  int32_t window;              /* W: 0 .. 8 */
+  uint32_t w_dist, w_rough;    /* <= 4095 each */
+  uint32_t rough_cap;          /* <= 65535 */
+  uint32_t max_points;         /* the records of the largest call the session is meant for: it sizes the reducing blocks;
+                                  0 = size by the device.  A larger call stays correct: blocks walk more shares */
+  uint32_t reserved[3];        /* zero */
+} d2pc_sectors_ground_config;
+/* 16 x 16 cells of 0.5, quantum 0.002, axes {1, 2, 3} (ENU), min_count 4, max_spread_q2 625 (a standard deviation of
+ * 0.05), max_step_q 50 (0.1), window 1, w_dist 1, w_rough 1, rough_cap 65535, max_points 0, device 0. */
+void d2pc_sectors_ground_config_init(d2pc_sectors_ground_config *gcfg);
+
+typedef struct d2pc_sectors_ground_geometry_t {
+  int32_t n_cells;             /* n_a * n_b: entries of every per-cell output */
+  float inv_c, inv_q;          /* as the specification forms them */
+  int32_t share_points;        /* D2PC_SECTORS_SHARE_POINTS */
+  int32_t blocks_per_cu;       /* reducing blocks per compute unit: as many as 160 KiB of LDS hold, 4 at the most */
+  int32_t blocks;              /* reducing blocks of a session on an MI355X (256 compute units): one per 4 shares of
+                                  max_points, 1 .. blocks_per_cu x compute units; all of them for max_points 0 */
+  size_t lds_bytes;            /* of one reducing block: 20 bytes per cell */
+  size_t block_bytes;          /* device memory the session holds PER BLOCK: its slab of partial cells, 20 bytes per cell,
+                                  rounded up to a multiple of 8 for an odd n_cells (5 x 3 cells: 304, not 300) */
+  size_t device_bytes;         /* what a session holds on an MI355X: the slabs and 13 bytes per cell between the launches */
+  int32_t reserved[4];
+} d2pc_sectors_ground_geometry_t;
+/* Host arithmetic only, no device.  The refusals are d2pc_sectors_ground_create's.  D2PC_ERR_INVALID_ARG: NULL,
+ * struct_size, axes, a cell_size or quantum that is NaN, not finite, zero or negative, min_count < 1, max_step_q >
+ * 65535, a weight > 4095, rough_cap > 65535, a reserved word that is not zero.  D2PC_ERR_BAD_SIZE: n_a or n_b outside
+ * 2 .. 64, window outside 0 .. 8, an inv_c or inv_q that is not a positive finite float. */
+int d2pc_sectors_ground_geometry(const d2pc_sectors_ground_config *gcfg, d2pc_sectors_ground_geometry_t *out);
+/* Host only, in double: max_spread_q2 from a standard deviation in the cloud's unit, floor((std / quantum)^2) clamped to
+ * 0xFFFFFFFE.  0 for a quantum that is not finite and > 0 or a std that is NaN or negative. */
+uint32_t d2pc_sectors_ground_spread_of_std(double quantum, double std_dev);
+
+typedef struct d2pc_sectors_ground_step {   /* 80 bytes in DEVICE memory: a captured graph replays with a new pose after one small copy */
+  float R[9];                  /* row-major: world = R p + t for a point p in the frame of `points` */
+  float t[3];
+  float origin[3];             /* a0, b0: the grid's corner; h0: the reference height */
+  uint32_t goal_i, goal_j;     /* the cell the cost measures from; a goal_i >= n_a or a goal_j >= n_b switches the term off */
+  uint32_t reserved[3];
+} d2pc_sectors_ground_step;
+
+typedef d2pc_sectors_steer_candidate d2pc_sectors_ground_candidate;   /* as a little-endian uint64: (cost << 32) | cell */
+
+typedef struct d2pc_sectors_ground d2pc_sectors_ground;
+/* Allocates everything the session will ever need (the blocks' slabs and 13 bytes per cell that the launches hand on).
+ * D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
+int d2pc_sectors_ground_create(const d2pc_sectors_ground_config *gcfg, d2pc_sectors_ground **out);
+int d2pc_sectors_ground_destroy(d2pc_sectors_ground *g);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_ground_last_error(const d2pc_sectors_ground *g);
+/* Reducing blocks this session holds slabs for (0 for NULL): geometry's arithmetic with the device's compute units.  A call
+ * launches min(blocks, its shares) of them. */
+int d2pc_sectors_ground_blocks(const d2pc_sectors_ground *g);
+
+typedef struct d2pc_sectors_ground_desc {   /* the clouds exactly as d2pc_sectors_desc takes them */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_ground_desc) */
+  int32_t point_step;          /* 16 or 32 */
+  int32_t n_clouds;            /* 1 .. 65,535 */
+  int32_t n_candidates;        /* 1 .. 32 when `candidates` is given */
+  const void *points;          /* DEVICE: the records, 16-byte aligned */
+  const uint32_t *counts;      /* DEVICE, nullable: as d2pc_sectors_desc (clamped to cloud_points; 0xFFFFFFFF reads as 0) */
+  size_t cloud_points;         /* 1 .. 2^32 - 1 */
+  size_t points_frame_stride_points;
+  const d2pc_sectors_ground_step *step;   /* DEVICE, 4-byte aligned */
+  const uint8_t *allowed;      /* DEVICE, nullable: one byte per cell, zero = no site */
+  uint32_t *count;             /* DEVICE out, each nullable; at least one of the nine is given */
+  int64_t *sum;                /* 8-byte aligned */
+  uint64_t *sum2;              /* 8-byte aligned */
+  int32_t *mean_q;
+  uint32_t *spread_q2;
+  uint8_t *flat;
+  uint8_t *site;
+  d2pc_sectors_ground_candidate *candidates;   /* n_candidates records, 8-byte aligned */
+  uint32_t *summary;           /* 4 words */
+} d2pc_sectors_ground_desc;
+/* struct_size, point_step 16, n_clouds 1, n_candidates 1; everything else zero. */
+void d2pc_sectors_ground_desc_init(d2pc_sectors_ground_desc *desc);
+/* Host only: what d2pc_sectors_ground_process_device refuses of `desc` for a session of `gcfg`, without a session; first
+ * the refusals of `gcfg`.  D2PC_ERR_INVALID_ARG: NULL, struct_size, point_step, n_clouds, a NULL points or step, no output,
+ * n_candidates out of 1 .. 32 when candidates is given, points not 16-byte aligned, another pointer not aligned to its type
+ * (8 bytes for sum, sum2 and candidates), an output that overlaps points, counts, step, allowed or another output.
+ * D2PC_ERR_BAD_SIZE: cloud_points, the frame stride and the largest position as d2pc_sectors_desc_check refuses them. */
+int d2pc_sectors_ground_desc_check(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_ground_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): three launches (two when neither site, candidates nor summary
+ * is asked for), no memset, no allocation, no count read on the host -- it can be captured into a graph as it is, behind
+ * its producer.  Every refusal is made before anything is enqueued.  Bit-reproducible: every sum is of integers.
+ * The slabs belong to the session: one call of a session in flight per stream order; two streams need two sessions.
+ */
+int d2pc_sectors_ground_process_device(d2pc_sectors_ground *g, const d2pc_sectors_ground_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

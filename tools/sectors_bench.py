@@ -47,6 +47,15 @@ ranks them).  GPU box only.
                                             With --parent NAME also T and T32 of libd2pc_sectors_NAME.so, another build of the steer's
                                             kernel (`make sectors SNAME=butterfly SDEFS=-DD2PC_SECTORS_STEER_FORM=0`: the form of the
                                             candidate rounds that lost), its outputs compared bit for bit with this build's first
+  python tools/sectors_bench.py --ground
+                                        ->  profiles/sectors_ground_bench.txt: the landing grid (d2pc_sectors_ground_process_device, three
+                                            launches) on a level ground under a camera that looks down: G = the call alone, G0 = with a
+                                            count of 0 (the fixed part), C = the copy of the bytes G reads, S / S0 = the 72 x 1 sectors call
+                                            on the same cloud, for 16 x 16 and 64 x 64 cells, the one-camera frame and the rig's merged
+                                            cloud, in producer order and shuffled, in ONE interleaved run.  Where libd2pc_sectors_gwave.so
+                                            and libd2pc_sectors_gplain.so are built (`make sectors SNAME=gwave
+                                            SDEFS=-DD2PC_SECTORS_GROUND_FORCE_ROUNDS=2`, `... SNAME=gplain ...=0`) the two forms of the
+                                            reduction stand beside it, their outputs compared bit for bit with the product's first
 """
 import argparse
 import os
@@ -624,6 +633,101 @@ def steer(a):
     return lines
 
 
+def ground(a):
+    """The landing grid beside the sectors call on the same cloud, and the two forms of its reduction when both are built."""
+    prop = torch.cuda.get_device_properties(0)
+    have_ab = all(os.path.exists(d2pc.sectors_library_path(v)) for v in ("gwave", "gplain"))
+    size = os.path.getsize(d2pc.sectors_library_path())
+    lines = ["# tools/sectors_bench.py --ground --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; arms interleaved round by round); libd2pc_sectors.so is %d bytes" % (
+                 prop.name, prop.multi_processor_count, size),
+             "# the frames are a level ground 5.4 m below a camera that looks straight down (disparity 94 .. 98, 30 % holes), the pose in the step is",
+             "# that nadir pose: a row of 64 neighbouring records spans about 0.5 m.  The grid is 8 m x 8 m under the camera: 16 x 16 cells of 0.5 m or",
+             "# 64 x 64 of 0.125 m, quantum 0.002, all nine outputs with 5 candidates, max_points = the cloud's capacity; a cell is flat up to a standard",
+             "# deviation of 0.15 m (the quantised depths spread by 0.08 m) and max_step_q is 100, so the one-camera frame makes sites and all 5 candidate rounds run (the line under a row says how many).  Of the rig's merged cloud only",
+             "# the camera that looks down and its neighbours reach the grid; the other records are gated out after the transform.",
+             "# G = d2pc_sectors_ground_process_device alone (three launches); G0 = the same call with a count of 0: the fixed part;",
+             "# C = d2pc_membench_copy moving the bytes G reads (16 B per record); S / S0 = the 72 x 1 sectors call on the same cloud / with a count of 0;",
+             "# wave / plain = libd2pc_sectors_gwave.so / _gplain.so (-DD2PC_SECTORS_GROUND_FORCE_ROUNDS=2 / =0), outputs compared bit for bit with G's first" if have_ab
+             else "# (libd2pc_sectors_gwave.so / _gplain.so are not built: no A/B columns)",
+             "# us per call: median (min .. max) over the rounds",
+             "%-52s %9s %6s %-30s %-30s %-30s %-30s %-30s %5s %5s %6s" % ("cloud, grid", "records", "blocks", "G", "G0", "C", "S", "S0", "G/C", "G/S", "G0/S0") +
+             (" %-30s %-30s %10s" % ("wave", "plain", "plain/wave") if have_ab else "")]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    nadir = np.array([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]])
+    for name, n, w, h, mode, rig_case, holes in CASES[:2]:
+        with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx, d2pc.Sectors() as sec:
+            prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+            level = torch.randint(94, 99, (n, h, w), generator=gen, device="cuda", dtype=torch.int32).to(torch.uint8)
+            level[prod.frames == 0] = 0
+            prod.frames = level
+            prod(s)
+            torch.cuda.synchronize()
+            ctx.check_async_error()
+            npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n]) if rig_case else int(prod.counts.cpu().numpy().view(np.uint32)[0])
+            ordered = prod.pts[:npts].clone()
+            # the grid's corner from camera 0's own records: 4 m to either side of their median, h0 at their median height
+            mid = np.median(ordered[:min(npts, prod.roi_n // 2), :3].cpu().numpy().astype(np.float64) @ nadir.T + [0.0, 0.0, 10.0], axis=0)
+            step = torch.from_numpy(d2pc.sectors_ground_step(nadir, [0.0, 0.0, 10.0], [np.round(mid[0]) - 4.0, np.round(mid[1]) - 4.0, mid[2]], 8, 8)
+                                    .view(np.int32).copy()).to("cuda")
+            shuffled = ordered[torch.randperm(npts, generator=gen, device="cuda")].contiguous()
+            count = torch.tensor([npts], dtype=torch.int32, device="cuda")
+            zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+            half = max(16 * npts // 2 // 16 * 16, 16)
+            src = torch.empty(half, dtype=torch.uint8, device="cuda")
+            dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+            s_out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"), count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                         nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"), distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
+            for grid in (dict(n_a=16, n_b=16, cell_size=0.5), dict(n_a=64, n_b=64, cell_size=0.125)):
+                grid = dict(grid, max_points=prod.cap, max_spread_q2=d2pc.sectors_ground_spread_of_std(0.002, 0.15), max_step_q=100)
+                sessions = [d2pc.SectorsGround(**grid)]
+                if have_ab:
+                    sessions += [d2pc.SectorsGround(variant=v, **grid) for v in ("gwave", "gplain")]
+                nc = sessions[0].n_cells
+
+                def outputs():
+                    return dict(count=torch.empty(nc, dtype=torch.int32, device="cuda"), sum=torch.empty(nc, dtype=torch.int64, device="cuda"),
+                                sum2=torch.empty(nc, dtype=torch.int64, device="cuda"), mean_q=torch.empty(nc, dtype=torch.int32, device="cuda"),
+                                spread_q2=torch.empty(nc, dtype=torch.int32, device="cuda"), flat=torch.empty(nc, dtype=torch.uint8, device="cuda"),
+                                site=torch.empty(nc, dtype=torch.uint8, device="cuda"), candidates=torch.empty(5, dtype=torch.int64, device="cuda"),
+                                summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+
+                outs = [outputs() for _ in sessions]
+                for label, cloud in (("producer order", ordered), ("shuffled", shuffled)):
+                    def call(g, o, c):
+                        return lambda: g.process(cloud, npts, step, counts=c, n_candidates=5, stream_ptr=s, **o)
+
+                    arms = [call(sessions[0], outs[0], count), call(sessions[0], outs[0], zero),
+                            lambda: ctx.membench_copy(src.data_ptr(), dst.data_ptr(), half, s),
+                            lambda: sec.process(cloud, npts, counts=count, stream_ptr=s, **s_out),
+                            lambda: sec.process(cloud, npts, counts=zero, stream_ptr=s, **s_out)]
+                    arms += [call(g, o, count) for g, o in zip(sessions[1:], outs[1:])]
+                    for fn in arms[:1] + arms[2:]:
+                        fn()
+                    torch.cuda.synchronize()
+                    summary = tuple(int(v) for v in outs[0]["summary"].cpu().numpy().view(np.uint32)[:3])
+                    assert 0 < summary[0] <= npts, "no record reached the grid"
+                    assert rig_case or summary[2] >= 5, "the one-camera frame makes fewer sites than candidates"
+                    assert all(torch.equal(outs[0][k], o[k]) for o in outs[1:] for k in o), "the builds disagree"
+                    iters = int(min(max(a.iters, 30000.0 / timed(arms[0], 5)), 4000))
+                    t = interleaved(arms, a.rounds, iters)
+                    ctx.check_async_error()
+                    m = [float(np.median(x)) for x in t]
+                    lines.append("%-52s %9d %6d %-30s %-30s %-30s %-30s %-30s %5.2f %5.2f %6.2f" % (
+                        "%s, %d x %d, %s" % (name[:14].strip(), grid["n_a"], grid["n_b"], label), npts, min(sessions[0].blocks, (npts + 1023) // 1024),
+                        fmt(t[0]), fmt(t[1]), fmt(t[2]), fmt(t[3]), fmt(t[4]), m[0] / m[2], m[0] / m[3], m[1] / m[4]) +
+                        (" %-30s %-30s %10.2f" % (fmt(t[5]), fmt(t[6]), m[6] / m[5]) if have_ab else ""))
+                    lines.append("#   %d of the records took part, %d flat cells, %d sites" % summary)
+                    print(lines[-2], flush=True)
+                for g in sessions:
+                    g.close()
+            prod.close()
+        del prod, ordered, shuffled, src, dst
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -633,13 +737,20 @@ def main():
     ap.add_argument("--elevation", action="store_true", help="elevation layers beside height layers instead of the cost table")
     ap.add_argument("--memory", action="store_true", help="the memory's update beside the sectors call instead of the cost table")
     ap.add_argument("--steer", action="store_true", help="the steer call beside the sectors call and the memory's update instead of the cost table")
+    ap.add_argument("--ground", action="store_true", help="the landing grid beside the sectors call instead of the cost table")
     ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
                     "alone, the table of this build against it (S of four grids, M of two)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.parent and (a.memory or a.ab):
+    if a.parent and (a.memory or a.ab or a.ground):
         ap.error("--parent goes with --elevation or --steer or stands alone (its own table holds the memory's rows)")
     versus = bool(a.parent) and not (a.memory or a.elevation or a.ab or a.steer)
+    if a.ground:
+        lines, out = ground(a), a.out or os.path.join(ROOT, "profiles", "sectors_ground_bench.txt")
+        with open(out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        print("wrote", out)
+        return
     out = a.out or os.path.join(ROOT, "profiles", "sectors_steer_bench.txt" if a.steer else "sectors_memory_bench.txt" if a.memory else "sectors_elevation_bench.txt" if a.elevation else "sectors_ab.txt" if a.ab else "sectors_refactor_bench.txt" if versus else "sectors_bench.txt")
     lines = steer(a) if a.steer else memory(a) if a.memory else elevation(a) if a.elevation else ab(a) if a.ab else parent(a) if versus else bench(a)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)

@@ -25,11 +25,13 @@
 //                    (2W + 1)^2 walk, cost and key in registers, the K smallest keys with the steer's rounds (DPP minima of
 //                    cost then cell, one 64-bit LDS min into the round's own word, one barrier a round), the summary from
 //                    wave reductions.  It reads what the merge wrote behind a kernel boundary: no global atomic.
+//                    The stage itself, and the merge's per-cell formula, are d2pc_sectors_ground_sites.hpp's: the terrain's
+//                    kernel (d2pc_sectors_terrain.hip) runs the same two on a window's sums.
 // Every accumulated value is an integer: the result is the same bytes whatever order lanes, waves and blocks arrive in.
 // Every float expression of the specification is rounded once: contraction is off in this file.
 #include <hip/hip_runtime.h>
 
-#include "d2pc_sectors_ground_plan.hpp"
+#include "d2pc_sectors_ground_sites.hpp"
 
 namespace d2pc {
 namespace sectors {
@@ -43,7 +45,6 @@ constexpr int kGroundWaveRounds = D2PC_SECTORS_GROUND_FORCE_ROUNDS;
 constexpr int kGroundWaveRounds = 0;
 #endif
 constexpr uint32_t kNoCell = 0xFFFFFFFFu;
-constexpr unsigned long long kNoKey = ~0ull;
 
 struct GroundArgs {   // GroundLaunch without its host-only members
   const uint4 *points;
@@ -85,23 +86,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   D2PC_GROUND_DPP_ADD(0x142, 0xa);
   D2PC_GROUND_DPP_ADD(0x143, 0xc);
 #undef D2PC_GROUND_DPP_ADD
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
-
-// the wave's minimum of a 32-bit word in every lane (d2pc_sectors_steer.hip's, copied: the kernels share no code)
-__device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
-#define D2PC_GROUND_DPP_MIN(ctrl, rows)                                                             \
-  {                                                                                                 \
-    const uint32_t o = uint32_t(__builtin_amdgcn_update_dpp(-1, int(v), ctrl, rows, 0xf, false));   \
-    v = o < v ? o : v;                                                                              \
-  }
-  D2PC_GROUND_DPP_MIN(0x111, 0xf)
-  D2PC_GROUND_DPP_MIN(0x112, 0xf)
-  D2PC_GROUND_DPP_MIN(0x114, 0xf)
-  D2PC_GROUND_DPP_MIN(0x118, 0xf)
-  D2PC_GROUND_DPP_MIN(0x142, 0xa)
-  D2PC_GROUND_DPP_MIN(0x143, 0xc)
-#undef D2PC_GROUND_DPP_MIN
   return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
 }
 
@@ -233,15 +217,8 @@ __global__ __launch_bounds__(kThreads) void k_ground_merge(const GroundArgs a) {
     }
   }
   if (slice != 0 || cell >= n_cells) return;
-  uint32_t mean = D2PC_SECTORS_GROUND_EMPTY_MEAN, spread = D2PC_SECTORS_GROUND_EMPTY_SPREAD;
-  if (cnt != 0u) {
-    const long long total = static_cast<long long>(sum), c = static_cast<long long>(cnt);
-    long long m = total / c;
-    m -= (total % c != 0 && total < 0) ? 1 : 0;   // floor division towards -inf
-    const unsigned long long um = static_cast<unsigned long long>(m);
-    const unsigned long long S = sum2 - 2ull * um * sum + static_cast<unsigned long long>(cnt) * um * um;   // wrapping: exact
-    mean = uint32_t(int(m)), spread = uint32_t(S / static_cast<unsigned long long>(cnt));
-  }
+  uint32_t mean, spread;
+  ground_cell_formula(cnt, sum, sum2, &mean, &spread);   // (d2pc_sectors_ground_sites.hpp: the terrain's formula too)
   const uint8_t flat = cnt >= a.min_count && spread <= a.max_spread_q2 ? 1 : 0;   // (min_count >= 1: an empty cell is never flat)
   if (a.count) a.count[cell] = cnt;
   if (a.sum) a.sum[cell] = sum;
@@ -254,15 +231,11 @@ __global__ __launch_bounds__(kThreads) void k_ground_merge(const GroundArgs a) {
 }
 
 __global__ __launch_bounds__(kGroundSiteThreads) void k_ground_sites(const GroundArgs a) {
-  __shared__ int mean_s[kGroundMaxCells];
-  __shared__ uint8_t flat_s[kGroundMaxCells];
-  __shared__ unsigned long long winner[D2PC_SECTORS_GROUND_MAX_CANDIDATES];   // round r's own word
-  __shared__ uint32_t slot[3][kGroundSiteWaves];
-  const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
-  const int n_cells = a.n_cells, n_a = a.n_a, n_b = a.n_b, W = a.window;
-  if (tid < D2PC_SECTORS_GROUND_MAX_CANDIDATES) winner[tid] = kNoKey;   // (a barrier lies before the first min into it)
+  __shared__ GroundSiteLds lds;
+  const int tid = int(threadIdx.x);
+  const int n_cells = a.n_cells;
   const uint8_t *flat_g = reinterpret_cast<const uint8_t *>(a.hand_on + 3 * size_t(n_cells));
-  uint32_t points = 0, n_flat = 0, n_sites = 0;
+  uint32_t points = 0, n_flat = 0;
   uint32_t spread[kGroundPerLane] = {};
 #pragma unroll
   for (int k = 0; k < kGroundPerLane; ++k) {
@@ -270,82 +243,15 @@ __global__ __launch_bounds__(kGroundSiteThreads) void k_ground_sites(const Groun
     if (c >= n_cells) continue;
     const uint8_t f = flat_g[c];
     points += a.hand_on[c], n_flat += f;
-    mean_s[c] = int(a.hand_on[n_cells + c]), flat_s[c] = f;
+    lds.mean_q[c] = int(a.hand_on[n_cells + c]), lds.flat[c] = f;
     spread[k] = a.hand_on[2 * n_cells + c];
   }
-  const uint32_t goal_i = reinterpret_cast<const uint32_t *>(a.step)[15], goal_j = reinterpret_cast<const uint32_t *>(a.step)[16];
-  const bool measured = goal_i < uint32_t(n_a) && goal_j < uint32_t(n_b);
-  __syncthreads();
-
-  unsigned long long key[kGroundPerLane];
-#pragma unroll
-  for (int k = 0; k < kGroundPerLane; ++k) {
-    key[k] = kNoKey;
-    const int c = tid + k * kGroundSiteThreads;
-    if (c >= n_cells) continue;
-    const int j = c / n_a, i = c - j * n_a;
-    bool site = i - W >= 0 && i + W < n_a && j - W >= 0 && j + W < n_b && flat_s[c] != 0 && (!a.allowed || a.allowed[c] != 0);
-    if (site) {
-      const int m = mean_s[c], step = int(a.max_step_q);
-      for (int dj = -W; dj <= W; ++dj)
-        for (int di = -W; di <= W; ++di) {
-          const int o = c + dj * n_a + di;
-          if (flat_s[o] == 0) site = false;   // (an empty cell's mean is 0x80000000: no difference is formed with it)
-          if (site) {
-            const int d = mean_s[o] - m;   // of flat cells: |mean_q| <= 32767
-            site = (d < 0 ? -d : d) <= step;
-          }
-        }
-    }
-    if (a.site) a.site[c] = site ? 1 : 0;
-    if (site) {
-      const int di = i - int(goal_i), dj = j - int(goal_j);
-      const uint32_t dist = measured ? uint32_t(di * di + dj * dj) : 0u;
-      const uint32_t cost = a.w_dist * dist + a.w_rough * (spread[k] < a.rough_cap ? spread[k] : a.rough_cap);
-      key[k] = (static_cast<unsigned long long>(cost) << 32) | uint32_t(c);
-      ++n_sites;
-    }
-  }
-
-  // ---- the summary
-  if (a.summary) {   // (uniform: a kernel argument)
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      points += uint32_t(__shfl_xor(int(points), m, 64));
-      n_flat += uint32_t(__shfl_xor(int(n_flat), m, 64));
-      n_sites += uint32_t(__shfl_xor(int(n_sites), m, 64));
-    }
-    if (lane == 0) slot[0][wave] = points, slot[1][wave] = n_flat, slot[2][wave] = n_sites;
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t t0 = 0, t1 = 0, t2 = 0;
-      for (int w = 0; w < kGroundSiteWaves; ++w) t0 += slot[0][w], t1 += slot[1][w], t2 += slot[2][w];
-      a.summary[0] = t0, a.summary[1] = t1, a.summary[2] = t2, a.summary[3] = 0u;
-    }
-  }
-
-  // ---- the K smallest keys, ascending (the steer's rounds)
-  unsigned long long head = key[0];   // the lane's smallest key not yet chosen
-#pragma unroll
-  for (int k = 1; k < kGroundPerLane; ++k) head = key[k] < head ? key[k] : head;
-  for (int r = 0; r < a.n_candidates; ++r) {
-    const uint32_t head_cost = uint32_t(head >> 32), head_cell = uint32_t(head);   // (all ones for no key: no cost is)
-    const uint32_t least = wave_umin(head_cost);
-    const uint32_t cell = wave_umin(head_cost == least ? head_cell : 0xFFFFFFFFu);
-    if (lane == 0 && least != 0xFFFFFFFFu) atomicMin(&winner[r], (static_cast<unsigned long long>(least) << 32) | cell);
-    __syncthreads();
-    const unsigned long long best = winner[r];   // (the same value in every lane)
-    if (best == kNoKey) {   // no site is left: all ones from here on
-      if (tid < a.n_candidates - r) a.candidates[r + tid] = kNoKey;
-      break;
-    }
-    if (tid == 0) a.candidates[r] = best;
-    if (head == best) {   // one lane of the block: its next key
-      head = kNoKey;
-#pragma unroll
-      for (int k = 0; k < kGroundPerLane; ++k) head = key[k] > best && key[k] < head ? key[k] : head;
-    }
-  }
+  GroundSiteStage st;
+  st.n_a = a.n_a, st.n_b = a.n_b, st.n_cells = n_cells, st.window = a.window, st.n_candidates = a.n_candidates;
+  st.max_step_q = a.max_step_q, st.w_dist = a.w_dist, st.w_rough = a.w_rough, st.rough_cap = a.rough_cap;
+  st.goal_i = reinterpret_cast<const uint32_t *>(a.step)[15], st.goal_j = reinterpret_cast<const uint32_t *>(a.step)[16];
+  st.allowed = a.allowed, st.site = a.site, st.candidates = a.candidates, st.summary = a.summary;
+  ground_site_stage(st, lds, spread, points, n_flat);   // (d2pc_sectors_ground_sites.hpp: the terrain's site stage too)
 }
 
 }  // namespace

@@ -31,6 +31,9 @@ SECTORS_SYMBOLS = [
     "d2pc_sectors_ground_config_init", "d2pc_sectors_ground_geometry", "d2pc_sectors_ground_spread_of_std", "d2pc_sectors_ground_create",
     "d2pc_sectors_ground_destroy", "d2pc_sectors_ground_last_error", "d2pc_sectors_ground_blocks", "d2pc_sectors_ground_desc_init",
     "d2pc_sectors_ground_desc_check", "d2pc_sectors_ground_process_device",
+    "d2pc_sectors_terrain_config_init", "d2pc_sectors_terrain_geometry", "d2pc_sectors_terrain_create", "d2pc_sectors_terrain_destroy",
+    "d2pc_sectors_terrain_last_error", "d2pc_sectors_terrain_state", "d2pc_sectors_terrain_reset_device", "d2pc_sectors_terrain_desc_init",
+    "d2pc_sectors_terrain_desc_check", "d2pc_sectors_terrain_update_device",
 ]
 EMPTY_AGE, OLDEST_AGE = 0xFFFFFFFF, 0xFFFFFFFE   # the age word of an empty record; where an age saturates
 STEER_MAX_REACH_SECTORS, STEER_MAX_REACH_LAYERS, STEER_MAX_CANDIDATES, STEER_MAX_WEIGHT = 32, 16, 32, 4095
@@ -41,6 +44,7 @@ GROUND_MAX_CELLS_PER_AXIS, GROUND_MAX_WINDOW, GROUND_MAX_CANDIDATES, GROUND_MAX_
 GROUND_EMPTY_MEAN, GROUND_EMPTY_SPREAD = 0x80000000, 0xFFFFFFFF   # mean_q (as a uint32) and spread_q2 of an empty cell
 GROUND_OFF = 0xFFFFFFFF           # a goal_i / goal_j that switches the distance term off
 GROUND_NO_CANDIDATE = 0xFFFFFFFFFFFFFFFF  # a candidate slot beyond the sites
+TERRAIN_MAX_DEPTH, TERRAIN_HEADER_BYTES, TERRAIN_MAX_CORNER = 16, 16, 536870912
 
 
 class SectorsConfig(ctypes.Structure):
@@ -152,6 +156,27 @@ class SectorsGroundDesc(ctypes.Structure):
     ]
 
 
+class SectorsTerrainConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("depth", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 6)]
+
+
+class SectorsTerrainGeometry(ctypes.Structure):
+    _fields_ = [
+        ("n_cells", ctypes.c_int32), ("inv_c", ctypes.c_float), ("slot_bytes", ctypes.c_size_t), ("state_bytes", ctypes.c_size_t),
+        ("headers_offset", ctypes.c_size_t), ("tables_offset", ctypes.c_size_t), ("reserved", ctypes.c_int32 * 6),
+    ]
+
+
+class SectorsTerrainDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("n_candidates", ctypes.c_int32), ("step", ctypes.c_void_p), ("frame_count", ctypes.c_void_p),
+        ("frame_sum", ctypes.c_void_p), ("frame_sum2", ctypes.c_void_p), ("allowed", ctypes.c_void_p), ("count", ctypes.c_void_p),
+        ("sum", ctypes.c_void_p), ("sum2", ctypes.c_void_p), ("mean_q", ctypes.c_void_p), ("spread_q2", ctypes.c_void_p),
+        ("flat", ctypes.c_void_p), ("site", ctypes.c_void_p), ("candidates", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -236,6 +261,21 @@ def load_sectors_library(variant=None):
         L.d2pc_sectors_ground_desc_init.restype = None
         L.d2pc_sectors_ground_desc_check.argtypes = [gcfg, gdesc]
         L.d2pc_sectors_ground_process_device.argtypes = [vp, gdesc, vp]
+    if variant is None or hasattr(L, "d2pc_sectors_terrain_create"):   # (an A/B variant may be a build from before the terrain)
+        gcfg, tcfg, tdesc = ctypes.POINTER(SectorsGroundConfig), ctypes.POINTER(SectorsTerrainConfig), ctypes.POINTER(SectorsTerrainDesc)
+        L.d2pc_sectors_terrain_config_init.argtypes = [tcfg]
+        L.d2pc_sectors_terrain_config_init.restype = None
+        L.d2pc_sectors_terrain_geometry.argtypes = [gcfg, tcfg, ctypes.POINTER(SectorsTerrainGeometry)]
+        L.d2pc_sectors_terrain_create.argtypes = [gcfg, tcfg, ctypes.POINTER(vp)]
+        L.d2pc_sectors_terrain_destroy.argtypes = [vp]
+        L.d2pc_sectors_terrain_last_error.argtypes = [vp]
+        L.d2pc_sectors_terrain_last_error.restype = ctypes.c_char_p
+        L.d2pc_sectors_terrain_state.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        L.d2pc_sectors_terrain_reset_device.argtypes = [vp, vp]
+        L.d2pc_sectors_terrain_desc_init.argtypes = [tdesc]
+        L.d2pc_sectors_terrain_desc_init.restype = None
+        L.d2pc_sectors_terrain_desc_check.argtypes = [gcfg, tcfg, tdesc]
+        L.d2pc_sectors_terrain_update_device.argtypes = [vp, tdesc, vp]
     if variant is None:
         _lib = L
     return L
@@ -588,3 +628,91 @@ class SectorsGround(_Session):
             cloud_points=cloud_points, points_frame_stride_points=frame_stride_points, step=_ptr(step), allowed=_ptr(allowed),
             count=_ptr(count), sum=_ptr(sum), sum2=_ptr(sum2), mean_q=_ptr(mean_q), spread_q2=_ptr(spread_q2), flat=_ptr(flat),
             site=_ptr(site), candidates=_ptr(candidates), summary=_ptr(summary)), stream_ptr)
+
+
+def sectors_terrain_config_init(**kw) -> SectorsTerrainConfig:
+    """d2pc_sectors_terrain_config_init, then the given fields."""
+    c = SectorsTerrainConfig()
+    load_sectors_library().d2pc_sectors_terrain_config_init(ctypes.byref(c))
+    return _set(c, kw)
+
+
+def sectors_terrain_desc_init(**kw) -> SectorsTerrainDesc:
+    """d2pc_sectors_terrain_desc_init, then the given fields."""
+    d = SectorsTerrainDesc()
+    load_sectors_library().d2pc_sectors_terrain_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_terrain_geometry(gcfg: SectorsGroundConfig, tcfg: SectorsTerrainConfig) -> SectorsTerrainGeometry:
+    """d2pc_sectors_terrain_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = SectorsTerrainGeometry()
+    st = load_sectors_library().d2pc_sectors_terrain_geometry(ctypes.byref(gcfg), ctypes.byref(tcfg), ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "sectors_terrain_geometry(%d x %d, depth %d)" % (gcfg.n_a, gcfg.n_b, tcfg.depth))
+    return g
+
+
+def sectors_terrain_desc_check(gcfg: SectorsGroundConfig, tcfg: SectorsTerrainConfig, desc: SectorsTerrainDesc) -> int:
+    """d2pc_sectors_terrain_desc_check: the status d2pc_sectors_terrain_update_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_terrain_desc_check(ctypes.byref(gcfg), ctypes.byref(tcfg), ctypes.byref(desc))
+
+
+class _StateView:
+    """A session's state block for torch.as_tensor."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "strides": None, "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+class SectorsTerrain(_Session):
+    """d2pc_sectors_terrain_*: the ground's per-cell tables of the last `depth` frames, kept on the device, and the landing grid
+    of that scrolling window in one launch.  `update` takes torch tensors or raw device pointers, is asynchronous on `stream`
+    and allocates nothing."""
+
+    _PREFIX = "d2pc_sectors_terrain"
+
+    def __init__(self, gcfg: SectorsGroundConfig, tcfg: SectorsTerrainConfig = None, variant=None, **kw):
+        self.cfg = gcfg
+        self.tcfg = _set(tcfg, kw) if tcfg is not None else sectors_terrain_config_init(**kw)
+        self._create(variant, "sectors_terrain_create(%d x %d, depth %d)" % (gcfg.n_a, gcfg.n_b, self.tcfg.depth),
+                     ctypes.byref(self.cfg), ctypes.byref(self.tcfg))
+        self.geometry = sectors_terrain_geometry(self.cfg, self.tcfg)
+        self.n_cells, self.depth = self.geometry.n_cells, self.tcfg.depth
+
+    def state(self):
+        """d2pc_sectors_terrain_state: (the state block's device pointer, its bytes)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        st = self._L.d2pc_sectors_terrain_state(self._h, ctypes.byref(p), ctypes.byref(n))
+        if st:
+            raise D2pcError(st, self.last_error())
+        return p.value, n.value
+
+    def state_tensor(self):
+        """The state block as a torch uint8 tensor that VIEWS it (the CUDA array interface, no copy): `.clone()` saves a map and
+        `.copy_()` restores one, in stream order with the updates.  The view must not outlive the session."""
+        import torch
+
+        ptr, n = self.state()
+        return torch.as_tensor(_StateView(ptr, n), device="cuda:%d" % self.cfg.device_id)
+
+    def update_desc(self, desc: SectorsTerrainDesc, stream_ptr=None):
+        """d2pc_sectors_terrain_update_device."""
+        st = self._L.d2pc_sectors_terrain_update_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def update(self, step, frame_count, frame_sum, frame_sum2, allowed=None, count=None, sum=None, sum2=None, mean_q=None,
+               spread_q2=None, flat=None, site=None, candidates=None, n_candidates=1, summary=None, status=None, stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.update_desc(sectors_terrain_desc_init(
+            n_candidates=n_candidates, step=_ptr(step), frame_count=_ptr(frame_count), frame_sum=_ptr(frame_sum),
+            frame_sum2=_ptr(frame_sum2), allowed=_ptr(allowed), count=_ptr(count), sum=_ptr(sum), sum2=_ptr(sum2), mean_q=_ptr(mean_q),
+            spread_q2=_ptr(spread_q2), flat=_ptr(flat), site=_ptr(site), candidates=_ptr(candidates), summary=_ptr(summary),
+            status=_ptr(status)), stream_ptr)
+
+    def reset(self, stream_ptr=None):
+        """d2pc_sectors_terrain_reset_device."""
+        st = self._L.d2pc_sectors_terrain_reset_device(self._h, stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())

@@ -202,7 +202,7 @@
  *
  * Outputs of a cell, n_cells = n_a * n_b entries each, each nullable:
  *     count      uint32
- *     sum        int64, 8-byte aligned; the caller may add these across frames, exactly
+ *     sum        int64, 8-byte aligned; exact, so frames add up (the TERRAIN block does, on the device)
  *     sum2       uint64, 8-byte aligned; likewise
  *     mean_q     int32   m = floor(sum / count), floor division towards -inf, in quanta above h0; 0x80000000 for an
  *                        empty cell
@@ -226,6 +226,46 @@
  *
  * Summary.  uint32 x 4: the points that took part (the sum of count modulo 2^32), the number of flat cells, the number
  * of sites, 0.
+ *
+ * ----------------------------------------------------------------------------------- TERRAIN (d2pc_sectors_terrain_*)
+ * A landing planner judges "flat" from the last second of data, on a map that moves with the vehicle.  The terrain session
+ * keeps the per-cell tables (count, sum, sum2) of the last `depth` frames on the device, each with the world cell index of
+ * its grid's corner, and d2pc_sectors_terrain_update_device -- ONE launch of one block behind
+ * d2pc_sectors_ground_process_device -- stores the new frame's tables, sums the window as seen from the new corner and forms
+ * the GROUND block's per-cell outputs, sites, cost, candidates and summary from the window's sums.  Nothing is moved when
+ * the grid scrolls: a stored table stays in its own frame-local layout and is read at a shifted index.  The sums are of
+ * integers: for tables that ground calls wrote, the result is the same bytes as ONE ground call over all the window's clouds
+ * whose grids were placed at the new corner.  tests/sectors_terrain_ref.py restates it in numpy and Python integers.
+ *
+ * State (d2pc_sectors_terrain_state: one block of device memory, little-endian; two copies save and restore a map).
+ *     16 headers of 16 bytes at offset 0:  {int32 ia0, int32 jb0, float h0, uint32 seq}.  seq 0 means empty; the headers
+ *     at and beyond `depth` stay zero.  Then, from byte 256, `depth` tables of slot_bytes = 20 * n_cells rounded up to a
+ *     multiple of 16; table s belongs to header s and holds sum[n_cells] (int64), sum2[n_cells] (uint64), count[n_cells]
+ *     (uint32), in this order: the ground slab's.
+ *
+ * The update, from the step (the GROUND block's, the very one the ground call used: a0, b0, h0, goal_i, goal_j are read)
+ * and the frame's three tables as d2pc_sectors_ground_process_device wrote them.
+ *     1. Anchor.  ua = fl(a0 * inv_c), ub = fl(b0 * inv_c).  The frame is anchored iff |ua| <= 536870912.0f and |ub| <=
+ *        536870912.0f, compared in float (a NaN fails).  ia0 = (int)rintf(ua), jb0 = (int)rintf(ub), half to even.  The
+ *        caller keeps the corner on a multiple of the cell size.
+ *     2. Not anchored: the state is untouched; every per-cell output is that of an empty window (count, sum, sum2 0, mean_q
+ *        0x80000000, spread_q2 0xFFFFFFFF, flat 0, site 0), the candidates are all ones, the summary is zeros and
+ *        status = {the largest seq of headers 0 .. depth - 1, 0, 0, 0}.
+ *     3. Anchored.  The replaced slot v is the one with the smallest seq among slots 0 .. depth - 1, the lowest index on a
+ *        tie; q = the largest seq + 1.  If the largest seq is 0xFFFFFFFF all slots are first taken as empty: v = 0, q = 1,
+ *        and the headers 1 .. depth - 1 are stored as zeros.  Slot v becomes {ia0, jb0, h0, q} and a copy of the frame's
+ *        three tables.
+ *     4. Window of cell (i, j): the frame's entry at (i, j), always; plus, for every other slot s with seq != 0 and h0_s ==
+ *        h0 (float ==: +0.0 equals -0.0, a NaN matches nothing), its entry at (i + ia0 - ia0_s, j + jb0 - jb0_s) where that
+ *        lies inside the grid (the differences are formed in 64 bits).  count adds modulo 2^32, sum and sum2 modulo 2^64:
+ *        exactness is the ground's as long as the window holds fewer than 2^32 points.
+ *     5. mean_q, spread_q2, flat, the sites, the cost (the goal cell is relative to the current corner), the candidates and
+ *        the summary are the GROUND block's, word for word, applied to the window's count, sum and sum2; min_count,
+ *        max_spread_q2, max_step_q, window, the weights and rough_cap of the ground configuration now judge the WINDOW's
+ *        cells.
+ *     6. status = {q, the slots that took part (the frame included), (uint32)ia0, (uint32)jb0}.
+ *     7. The guarantee holds for tables that ground calls wrote.  For other tables the per-cell outputs follow the wrapping
+ *        formulas, and site / candidates are unspecified.
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -605,6 +645,85 @@ int d2pc_sectors_ground_desc_check(const d2pc_sectors_ground_config *gcfg, const
  * The slabs belong to the session: one call of a session in flight per stream order; two streams need two sessions.
  */
 int d2pc_sectors_ground_process_device(d2pc_sectors_ground *g, const d2pc_sectors_ground_desc *desc, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------ the terrain */
+#define D2PC_SECTORS_TERRAIN_MAX_DEPTH 16
+#define D2PC_SECTORS_TERRAIN_HEADER_BYTES 16        /* {int32 ia0, int32 jb0, float h0, uint32 seq} */
+#define D2PC_SECTORS_TERRAIN_MAX_CORNER 536870912   /* 2^29: the largest |corner| in cells that anchors a frame */
+
+typedef struct d2pc_sectors_terrain_config {   /* fixed for a terrain session, beside the ground configuration */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_terrain_config) */
+  int32_t depth;               /* 1 .. 16: the frames of the window, the newest included */
+  uint32_t reserved[6];        /* zero */
+} d2pc_sectors_terrain_config;
+/* depth 8. */
+void d2pc_sectors_terrain_config_init(d2pc_sectors_terrain_config *tcfg);
+
+typedef struct d2pc_sectors_terrain_geometry_t {
+  int32_t n_cells;             /* n_a * n_b */
+  float inv_c;                 /* as the specification forms it: the anchor's factor */
+  size_t slot_bytes;           /* one stored table: 20 * n_cells rounded up to a multiple of 16 */
+  size_t state_bytes;          /* the state block: 256 + depth * slot_bytes */
+  size_t headers_offset;       /* 0 */
+  size_t tables_offset;        /* 256: table s begins at tables_offset + s * slot_bytes */
+  int32_t reserved[6];
+} d2pc_sectors_terrain_geometry_t;
+/* Host arithmetic only, no device.  First the refusals of d2pc_sectors_ground_geometry for `gcfg`, unchanged; then, in this
+ * order, D2PC_ERR_INVALID_ARG: a NULL tcfg, its struct_size;  D2PC_ERR_BAD_SIZE: depth outside 1 .. 16;
+ * D2PC_ERR_INVALID_ARG: a reserved word that is not zero.  A NULL `out` is D2PC_ERR_INVALID_ARG before all of them. */
+int d2pc_sectors_terrain_geometry(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_terrain_config *tcfg,
+                                  d2pc_sectors_terrain_geometry_t *out);
+
+typedef struct d2pc_sectors_terrain d2pc_sectors_terrain;
+/* `gcfg` is the configuration the ground session was made from: its grid, cell_size, min_count, max_spread_q2, max_step_q,
+ * window, weights and rough_cap now apply to the WINDOW's cells (quantum, axes and max_points are checked and not used).
+ * Allocates the state once, with every header zero.  D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
+int d2pc_sectors_terrain_create(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_terrain_config *tcfg, d2pc_sectors_terrain **out);
+int d2pc_sectors_terrain_destroy(d2pc_sectors_terrain *t);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_terrain_last_error(const d2pc_sectors_terrain *t);
+/* The state block in DEVICE memory and its size (each nullable), laid out as the TERRAIN block documents: a caller saves and
+ * restores a map with one copy each way, in stream order with the updates. */
+int d2pc_sectors_terrain_state(const d2pc_sectors_terrain *t, void **device_ptr, size_t *bytes);
+/* Asynchronous on `stream`: one small launch that zeroes the 16 headers with vector stores (the window is empty again;
+ * the tables are left as they are, nothing reads a table of an empty header). */
+int d2pc_sectors_terrain_reset_device(d2pc_sectors_terrain *t, void *stream);
+
+typedef struct d2pc_sectors_terrain_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_terrain_desc) */
+  int32_t n_candidates;        /* 1 .. 32 when `candidates` is given */
+  const d2pc_sectors_ground_step *step;   /* DEVICE, 4-byte aligned: the very step the ground call used */
+  const uint32_t *frame_count; /* DEVICE in, all three required: n_cells entries each, as */
+  const int64_t *frame_sum;    /*   d2pc_sectors_ground_process_device wrote them (count, sum, sum2); */
+  const uint64_t *frame_sum2;  /*   frame_sum and frame_sum2 8-byte aligned */
+  const uint8_t *allowed;      /* DEVICE, nullable: one byte per cell, zero = no site */
+  uint32_t *count;             /* DEVICE out, the WINDOW's, each nullable; at least one of these ten is given */
+  int64_t *sum;                /* 8-byte aligned */
+  uint64_t *sum2;              /* 8-byte aligned */
+  int32_t *mean_q;
+  uint32_t *spread_q2;
+  uint8_t *flat;
+  uint8_t *site;
+  d2pc_sectors_ground_candidate *candidates;   /* n_candidates records, 8-byte aligned */
+  uint32_t *summary;           /* 4 words */
+  uint32_t *status;            /* 4 words: {seq, slots that took part, (uint32)ia0, (uint32)jb0} */
+} d2pc_sectors_terrain_desc;
+/* struct_size, n_candidates 1; everything else zero. */
+void d2pc_sectors_terrain_desc_init(d2pc_sectors_terrain_desc *desc);
+/* Host only: what d2pc_sectors_terrain_update_device refuses of `desc` for a session of `gcfg` and `tcfg`, without a
+ * session; first the refusals of the two configurations.  D2PC_ERR_INVALID_ARG: NULL, struct_size, a NULL step, frame_count,
+ * frame_sum or frame_sum2, no output, n_candidates out of 1 .. 32 when candidates is given, a pointer not aligned to its
+ * type (8 bytes for frame_sum, frame_sum2, sum, sum2 and candidates), an output that overlaps step, a frame table, allowed
+ * or another output.  The session adds one refusal: a buffer that overlaps its own state block. */
+int d2pc_sectors_terrain_desc_check(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_terrain_config *tcfg,
+                                    const d2pc_sectors_terrain_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): ONE launch of one block, no memset, no allocation, no host
+ * read -- it can be captured into a graph behind d2pc_sectors_ground_process_device.  Every refusal is made before anything
+ * is enqueued.  Bit-reproducible: every sum is of integers and every minimum is of distinct keys.  The state belongs to the
+ * session: one update of a session in flight per stream order.
+ */
+int d2pc_sectors_terrain_update_device(d2pc_sectors_terrain *t, const d2pc_sectors_terrain_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,12 @@ ranks them).  GPU box only.
                                             and libd2pc_sectors_gplain.so are built (`make sectors SNAME=gwave
                                             SDEFS=-DD2PC_SECTORS_GROUND_FORCE_ROUNDS=2`, `... SNAME=gplain ...=0`) the two forms of the
                                             reduction stand beside it, their outputs compared bit for bit with the product's first
+  python tools/sectors_bench.py --terrain
+                                        ->  profiles/sectors_terrain_bench.txt: the terrain's update (d2pc_sectors_terrain_update_device,
+                                            one launch of one block) alone on the ground call's tables, for 16 x 16 cells at depth 8 and
+                                            64 x 64 at depth 16, with every slot of the window taking part and with none, beside the ground
+                                            call's G and G0 and the steer call on the same one-camera cloud, in ONE interleaved run.  No
+                                            time is fixed in advance: T is read against G0 and G of its row
 """
 import argparse
 import os
@@ -728,6 +734,106 @@ def ground(a):
     return lines
 
 
+def terrain(a):
+    """The terrain's update alone beside the ground call that feeds it and the steer call, on one cloud, in one run."""
+    prop = torch.cuda.get_device_properties(0)
+    size = os.path.getsize(d2pc.sectors_library_path())
+    lines = ["# tools/sectors_bench.py --terrain --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round); libd2pc_sectors.so is %d bytes" % (
+                 prop.name, prop.multi_processor_count, size),
+             "# the cloud is tools/sectors_bench.py --ground's one-camera frame (a level ground under a nadir camera, 30 % holes) in producer order; the",
+             "# grid is 8 m x 8 m under the camera, all nine outputs with 5 candidates and status.",
+             "# G = d2pc_sectors_ground_process_device alone (three launches); G0 = the same call with a count of 0: the ground's fixed part;",
+             "# T all = d2pc_sectors_terrain_update_device alone (ONE launch of one block) on G's count / sum / sum2 with the corner held, so every slot",
+             "# of the window takes part (depth - 1 stored tables are read whole); T none = the same with a NaN h0 in the step: the frame is anchored and",
+             "# stored, no stored table matches it, the window is the frame alone; ST = d2pc_sectors_steer_device alone (72 x 1, reach 8, 5 candidates) on",
+             "# the distance_cm the sectors call and the memory's update made from the same cloud.  us per call: median (min .. max) over the rounds.",
+             "# No time was fixed in advance: T is read against G0 and G of its row",
+             "%-34s %9s %5s %-30s %-30s %-30s %-30s %-30s %8s %8s %8s" % ("cloud, grid x depth", "records", "took", "G", "G0", "T all", "T none", "ST",
+                                                                    "Tall/G0", "Tall/G", "Tnone/G0")]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    nadir = np.array([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]])
+    name, n, w, h, mode, rig_case, holes = CASES[0]
+    with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx, d2pc.Sectors() as sec:
+        prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+        level = torch.randint(94, 99, (n, h, w), generator=gen, device="cuda", dtype=torch.int32).to(torch.uint8)
+        level[prod.frames == 0] = 0
+        prod.frames = level
+        prod(s)
+        torch.cuda.synchronize()
+        ctx.check_async_error()
+        npts = int(prod.counts.cpu().numpy().view(np.uint32)[0])
+        cloud = prod.pts[:npts].clone()
+        mid = np.median(cloud[:min(npts, prod.roi_n // 2), :3].cpu().numpy().astype(np.float64) @ nadir.T + [0.0, 0.0, 10.0], axis=0)
+        corner = [np.round(mid[0]) - 4.0, np.round(mid[1]) - 4.0, float(np.float32(mid[2]))]   # a multiple of both cell sizes
+        step = torch.from_numpy(d2pc.sectors_ground_step(nadir, [0.0, 0.0, 10.0], corner, 8, 8).view(np.int32).copy()).to("cuda")
+        lone = torch.from_numpy(d2pc.sectors_ground_step(nadir, [0.0, 0.0, 10.0], corner[:2] + [np.nan], 8, 8).view(np.int32).copy()).to("cuda")
+        count = torch.tensor([npts], dtype=torch.int32, device="cuda")
+        zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+        # the steer's input: the sectors call and one update of the memory on the same cloud
+        mem = d2pc.SectorsMemory(sec.cfg, 2000)
+        st = d2pc.SectorsSteer(sec.cfg, max_reach_sectors=8, max_reach_layers=0)
+        so = dict(count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"), nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
+        mo = dict(distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
+        to = dict(clearance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"), cost=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
+                  candidates=torch.empty(5, dtype=torch.int64, device="cuda"), summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+        mstep = torch.from_numpy(d2pc.sectors_memory_step(np.eye(3), [0.0, 0.0, 0.0], 50).view(np.int32).copy()).to("cuda")
+        goal = torch.from_numpy(d2pc.sectors_steer_step(sec.cfg.n_sectors // 3, 0, 1, 0).view(np.int32).copy()).to("cuda")
+        sec.process(cloud, npts, stream_ptr=s, **so)
+        mem.update(cloud, npts, so["count"], so["nearest"], mstep, stream_ptr=s, **mo)
+        rows, arms, keep = [], [lambda: st.steer(mo["distance_cm"], goal, n_candidates=5, stream_ptr=s, **to)], []
+        for grid, depth in ((dict(n_a=16, n_b=16, cell_size=0.5), 8), (dict(n_a=64, n_b=64, cell_size=0.125), 16)):
+            grid = dict(grid, max_points=prod.cap, max_spread_q2=d2pc.sectors_ground_spread_of_std(0.002, 0.15), max_step_q=100)
+            g = d2pc.SectorsGround(**grid)
+            nc = g.n_cells
+
+            def outputs():
+                return dict(count=torch.empty(nc, dtype=torch.int32, device="cuda"), sum=torch.empty(nc, dtype=torch.int64, device="cuda"),
+                            sum2=torch.empty(nc, dtype=torch.int64, device="cuda"), mean_q=torch.empty(nc, dtype=torch.int32, device="cuda"),
+                            spread_q2=torch.empty(nc, dtype=torch.int32, device="cuda"), flat=torch.empty(nc, dtype=torch.uint8, device="cuda"),
+                            site=torch.empty(nc, dtype=torch.uint8, device="cuda"), candidates=torch.empty(5, dtype=torch.int64, device="cuda"),
+                            summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+
+            go, g0, t_all, t_none = outputs(), outputs(), outputs(), outputs()
+            status = [torch.zeros(4, dtype=torch.int32, device="cuda") for _ in range(2)]
+            ter = [d2pc.SectorsTerrain(g.cfg, depth=depth) for _ in range(2)]   # a window each: the two arms do not disturb each other
+            keep.append((g, ter, go, g0, t_all, t_none, status))
+            g.process(cloud, npts, step, counts=count, n_candidates=5, stream_ptr=s, **go)
+            arms += [lambda g=g, go=go: g.process(cloud, npts, step, counts=count, n_candidates=5, stream_ptr=s, **go),
+                     lambda g=g, g0=g0: g.process(cloud, npts, step, counts=zero, n_candidates=5, stream_ptr=s, **g0),
+                     lambda t=ter[0], go=go, o=t_all, st_=status[0]: t.update(step, go["count"], go["sum"], go["sum2"], n_candidates=5, status=st_, stream_ptr=s, **o),
+                     lambda t=ter[1], go=go, o=t_none, st_=status[1]: t.update(lone, go["count"], go["sum"], go["sum2"], n_candidates=5, status=st_, stream_ptr=s, **o)]
+            rows.append(("%s, %d x %d x %d" % (name[:14].strip(), grid["n_a"], grid["n_b"], depth), depth, status))
+        for _ in range(20):   # warm-up: code objects, and more updates than the deepest window holds
+            for fn in arms:
+                fn()
+        torch.cuda.synchronize()
+        ctx.check_async_error()
+        for row, depth, status in rows:
+            took = [int(x.cpu().numpy().view(np.uint32)[1]) for x in status]
+            assert took == [depth, 1], "%s: %s slots took part" % (row, took)
+        iters = int(min(max(a.iters, 30000.0 / timed(arms[1], 5)), 4000))
+        t = interleaved(arms, a.rounds, iters)
+        ctx.check_async_error()
+        lines.insert(-1, "# %d calls per timed window" % iters)
+        for k, (row, depth, status) in enumerate(rows):
+            G, G0, Ta, Tn = t[1 + 4 * k:5 + 4 * k]
+            m = [float(np.median(x)) for x in (G, G0, Ta, Tn)]
+            lines.append("%-34s %9d %5d %-30s %-30s %-30s %-30s %-30s %8.2f %8.2f %8.2f" % (
+                row, npts, depth, fmt(G), fmt(G0), fmt(Ta), fmt(Tn), fmt(t[0]), m[2] / m[1], m[2] / m[0], m[3] / m[1]))
+        for g, ter, *_ in keep:
+            for x in ter:
+                x.close()
+            g.close()
+        st.close()
+        mem.close()
+        prod.close()
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -738,15 +844,17 @@ def main():
     ap.add_argument("--memory", action="store_true", help="the memory's update beside the sectors call instead of the cost table")
     ap.add_argument("--steer", action="store_true", help="the steer call beside the sectors call and the memory's update instead of the cost table")
     ap.add_argument("--ground", action="store_true", help="the landing grid beside the sectors call instead of the cost table")
+    ap.add_argument("--terrain", action="store_true", help="the terrain's update beside the ground call and the steer call instead of the cost table")
     ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
                     "alone, the table of this build against it (S of four grids, M of two)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.parent and (a.memory or a.ab or a.ground):
+    if a.parent and (a.memory or a.ab or a.ground or a.terrain):
         ap.error("--parent goes with --elevation or --steer or stands alone (its own table holds the memory's rows)")
     versus = bool(a.parent) and not (a.memory or a.elevation or a.ab or a.steer)
-    if a.ground:
-        lines, out = ground(a), a.out or os.path.join(ROOT, "profiles", "sectors_ground_bench.txt")
+    if a.ground or a.terrain:
+        lines = terrain(a) if a.terrain else ground(a)
+        out = a.out or os.path.join(ROOT, "profiles", "sectors_terrain_bench.txt" if a.terrain else "sectors_ground_bench.txt")
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
         print("wrote", out)

@@ -20,8 +20,8 @@
 //                    band's two boundaries, counts the interior boundaries below the point in a second loop of the azimuth
 //                    loop's shape (one broadcast LDS read per boundary serves the lane's four records) and keys on d2.
 //                    Where a record falls (picks, gates, half turn, a step of either boundary count, the key's bits) is
-//                    d2pc_sectors_bin.hpp's, which the memory's kernel calls too; here are the loads, the two loops' skeletons
-//                    and the tables of cells.
+//                    d2pc_sectors_bin.hpp's, which the memory's kernel calls too; the walk over the shares and its loads, and
+//                    the wave minimum, are d2pc_sectors_device.hpp's; here are the two loops' skeletons and the tables of cells.
 // k_sectors_finish   min / sum over the slabs, coalesced across cells (8 cells x 32 slices of the slabs per block, a
 //                    tree through LDS over the slices), then the outputs the caller asked for.
 // Keys are integers and counts are sums of integers: the result is the same bytes whatever order lanes, waves and
@@ -39,8 +39,13 @@ namespace {
 constexpr int kFinishCells = 8, kFinishSlices = 32;
 static_assert(kFinishCells * kFinishSlices == kThreads, "the finishing block is cells x slices");
 
-struct Args {   // Launch without its host-only members
-  const uint4 *points;
+// Launch without its host-only members.  The walk's eight fields stand here one by one, where they stood before CloudWalk:
+// embedded as the struct (at the front, behind the outputs or at the end alike) hipcc of ROCm 7 allocates k_sectors_reduce
+// 64 / 52 VGPRs for 68 / 68 and schedules it anew, and S came out 2 to 7 % slower in all four rows
+// (profiles/sectors_shared_bench.txt).  With the fields here and the struct made of them in the kernel, the shared walk
+// compiles to the instruction stream it had.  GroundArgs embeds the struct: k_ground_reduce is the same either way.
+struct Args {
+  const void *points;
   const uint32_t *counts;
   const float2 *table;
   uint64_t *slab_keys;
@@ -53,21 +58,6 @@ struct Args {   // Launch without its host-only members
   int blocks, rounds;
   GridArgs grid;
 };
-
-// the minimum over the wave's 64 lanes, in every lane; all 64 lanes are active at every call (the callers' control
-// flow is uniform).  row_shr 1, 2, 4, 8 scan a row of 16; row_bcast:15 / :31 carry the rows' totals on: lane 63 holds all
-__device__ __forceinline__ uint32_t wave_umin(uint32_t v) {
-#define D2PC_DPP_MIN(ctrl, rows) \
-  v = min(v, uint32_t(__builtin_amdgcn_update_dpp(int(kNone), int(v), ctrl, rows, 0xf, false)))
-  D2PC_DPP_MIN(0x111, 0xf);
-  D2PC_DPP_MIN(0x112, 0xf);
-  D2PC_DPP_MIN(0x114, 0xf);
-  D2PC_DPP_MIN(0x118, 0xf);
-  D2PC_DPP_MIN(0x142, 0xa);
-  D2PC_DPP_MIN(0x143, 0xc);
-#undef D2PC_DPP_MIN
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
 
 // one record slot of the wave into the block's table
 __device__ __forceinline__ void merge(unsigned long long *keys, uint32_t *cnts, int rounds, uint32_t cell, uint32_t r2_bits,
@@ -110,31 +100,14 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
   for (int j = int(tid); j < g.half + (kElevation ? g.n_layers + 1 : 0); j += kThreads) tab[j] = a.table[j];
   __syncthreads();
 
-  for (uint64_t share = blockIdx.x; share < a.shares; share += uint64_t(a.blocks)) {
-    uint64_t cloud = 0;
-    uint32_t in_cloud = uint32_t(share);
-    if (a.n_clouds > 1) {
-      cloud = share / a.shares_per_cloud;
-      in_cloud = uint32_t(share - cloud * a.shares_per_cloud);
-    }
-    uint32_t n = a.cloud_points;
-    if (a.counts) {
-      const uint32_t given = a.counts[cloud];
-      n = given == 0xFFFFFFFFu ? 0u : min(given, a.cloud_points);
-    }
-    const uint32_t i0 = in_cloud * uint32_t(D2PC_SECTORS_SHARE_POINTS);   // (< 2^32: shares_per_cloud <= 2^22)
-    if (i0 >= n) continue;
-    const uint64_t first = cloud * a.stride;   // the cloud's first record in `points`; its position fits 32 bits
+  const CloudWalk walk = {a.points, a.counts, a.stride, a.shares, a.shares_per_cloud, a.cloud_points, a.n_clouds, a.step16};
+  for (uint64_t share = blockIdx.x; share < walk.shares; share += uint64_t(a.blocks)) {
+    ShareAt at;
+    if (!find_share(walk, share, &at)) continue;   // (d2pc_sectors_device.hpp)
     uint4 rec[kPerLane];
     bool have[kPerLane];
 #pragma unroll
-    for (int k = 0; k < kPerLane; ++k) {
-      const uint32_t i = i0 + uint32_t(k * kThreads) + tid;   // (i0 + 1,023 <= 2^32 - 1: no wrap)
-      have[k] = i < n;
-      rec[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (have[k]) rec[k] = a.points[(first + i) * a.step16];
-      asm volatile("" ::"v"(rec[k].w));   // keeps the load a whole 16-byte one (w is not used: it would shrink to 12)
-    }
+    for (int k = 0; k < kPerLane; ++k) rec[k] = share_record(walk, at, tid, k, &have[k]);
     // where the lane's four records fall (d2pc_sectors_bin.hpp)
     float f[kPerLane], l[kPerLane], up[kPerLane], hz[kPerLane];
     uint32_t cell[kPerLane], key_bits[kPerLane], sector[kPerLane], layer[kPerLane] = {};
@@ -156,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void k_sectors_reduce(const Args a) {
     }
 #pragma unroll
     for (int k = 0; k < kPerLane; ++k)
-      merge(keys, cnts, a.rounds, cell_of(g, cell[k], sector[k], layer[k]), key_bits[k], uint32_t(first) + i0 + uint32_t(k * kThreads) + tid);
+      merge(keys, cnts, a.rounds, cell_of(g, cell[k], sector[k], layer[k]), key_bits[k], share_position(at, tid, k));
   }
 
   __syncthreads();
@@ -220,12 +193,12 @@ int prepare_sectors_kernels(const Plan &p) {
 
 int launch_sectors(const Launch &in) {
   Args a;
-  a.points = static_cast<const uint4 *>(in.points), a.counts = in.counts;
+  const CloudWalk &w = in.walk;
+  a.points = w.points, a.counts = w.counts, a.stride = w.stride, a.shares = w.shares;
+  a.shares_per_cloud = w.shares_per_cloud, a.cloud_points = w.cloud_points, a.n_clouds = w.n_clouds, a.step16 = w.step16;
   a.table = reinterpret_cast<const float2 *>(in.table);
   a.slab_keys = in.slab_keys, a.slab_counts = in.slab_counts;
   a.range = in.range, a.count = in.count, a.nearest = in.nearest, a.distance_cm = in.distance_cm;
-  a.stride = in.stride, a.shares = in.shares;
-  a.shares_per_cloud = in.shares_per_cloud, a.cloud_points = in.cloud_points, a.n_clouds = in.n_clouds, a.step16 = in.step16;
   const Plan &p = in.plan;
   a.grid = grid_args(p), a.blocks = in.blocks;
 #ifdef D2PC_SECTORS_FORCE_ROUNDS

@@ -5,12 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "d2pc_sectors_plan.hpp"
+#include "d2pc_sectors_device.hpp"
 
 namespace d2pc {
 namespace sectors {
-
-constexpr uint32_t kNone = 0xFFFFFFFFu;   // the cell of a record that takes no part
 
 struct GridArgs {   // Plan without its host-only members
   int n_sectors, n_layers, n_cells, half;

@@ -125,13 +125,9 @@ int d2pc_sectors_process_device(d2pc_sectors *s, const d2pc_sectors_desc *d, voi
   if (!guard.ok) return fail(s->err, D2PC_ERR_NO_DEVICE, "cannot select device %d", s->device);
   Launch a;
   a.plan = s->plan;
-  a.points = d->points, a.counts = d->counts, a.table = s->d_table;
+  a.walk = cloud_walk(*d), a.table = s->d_table;
   a.slab_keys = s->d_slab_keys, a.slab_counts = s->d_slab_counts;
   a.range = d->range, a.count = d->count, a.nearest = d->nearest, a.distance_cm = d->distance_cm;
-  a.stride = d->n_clouds > 1 ? uint64_t(d->points_frame_stride_points) : 0;
-  a.cloud_points = uint32_t(d->cloud_points), a.n_clouds = uint32_t(d->n_clouds), a.step16 = uint32_t(d->point_step / 16);
-  a.shares_per_cloud = uint32_t((uint64_t(d->cloud_points) + D2PC_SECTORS_SHARE_POINTS - 1) / D2PC_SECTORS_SHARE_POINTS);
-  a.shares = uint64_t(a.shares_per_cloud) * uint64_t(a.n_clouds);
   a.blocks = s->blocks;
   a.stream = stream;   // NULL = HIP's default stream
   const hipError_t e = hipError_t(launch_sectors(a));

@@ -5,17 +5,8 @@
 //                    loads in flight per lane; a 32-byte record is the load of its first half).  About a dozen VALU
 //                    operations bin a record, so the LDS atomics are what it costs.  Each block keeps a private table of
 //                    the cells in dynamic LDS: sum (64-bit), sum2 (64-bit), count, 20 bytes per cell, and every lane issues
-//                    its own three LDS adds (the 64-bit add is native).  The other form is built behind one macro: a nadir
-//                    camera's row-major cloud puts the 64 neighbouring records of a wave into one or two cells, so a wave can
-//                    first reduce inside itself -- the cell of the first live lane is elected, the lanes that match it add up
-//                    their k (one 32-bit DPP sum) and their k * k (two DPP sums of 16-bit halves: 64 squares of up to 2^30
-//                    do not fit 32 bits) and ONE lane issues the three LDS adds; two such rounds, then per-lane adds for
-//                    the lanes still live.  Measured (profiles/sectors_ground_bench.txt), the per-lane form
-//                    wins in seven rows of eight, for 16 x 16 and for 64 x 64 cells, in producer order and shuffled (the rig's
-//                    merged cloud at 16 x 16 in producer order is the eighth, by 7 %): three DPP sums of six steps
-//                    each and two ballots a round cost more than the serialised adds they save.  So kGroundWaveRounds is 0
-//                    for every grid, at compile time: the product's kernel holds nothing of the rounds;
-//                    -DD2PC_SECTORS_GROUND_FORCE_ROUNDS=0 / =2 build the two arms (tools/sectors_bench.py --ground).
+//                    its own three LDS adds (the 64-bit add is native).  The other form, an in-wave pre-reduction of the
+//                    lanes that share a cell, lost in seven rows of eight and left the sources: DESIGN.md 8g.
 //                    At the end the block stores its table to its own slab with plain vector stores: no global atomic,
 //                    nothing to clear, no protocol between blocks.
 // k_ground_merge     sums over the slabs of the blocks that ran, 16 cells x 16 slices of the slabs per block (a row of 16
@@ -37,18 +28,8 @@ namespace d2pc {
 namespace sectors {
 namespace {
 
-// elected cells per wave and record slot: none in the product, as measured.  A compile-time constant: the product's kernel
-// holds no code of the rounds
-#ifdef D2PC_SECTORS_GROUND_FORCE_ROUNDS
-constexpr int kGroundWaveRounds = D2PC_SECTORS_GROUND_FORCE_ROUNDS;
-#else
-constexpr int kGroundWaveRounds = 0;
-#endif
-constexpr uint32_t kNoCell = 0xFFFFFFFFu;
-
 struct GroundArgs {   // GroundLaunch without its host-only members
-  const uint4 *points;
-  const uint32_t *counts;
+  CloudWalk walk;
   const float *step;
   const uint8_t *allowed;
   unsigned long long *slabs;
@@ -59,64 +40,25 @@ struct GroundArgs {   // GroundLaunch without its host-only members
   uint8_t *flat, *site;
   unsigned long long *candidates;
   uint32_t *summary;
-  uint64_t stride, shares;
-  uint32_t shares_per_cloud, cloud_points, n_clouds, step16;
   int blocks, n_candidates;
-  int n_a, n_b, n_cells, window;
+  GroundSiteGrid grid;
   int axis_a, axis_b, axis_h;
   uint32_t flip_a, flip_b, flip_h;
   float inv_c, inv_q;
-  uint32_t min_count, max_spread_q2, max_step_q, w_dist, w_rough, rough_cap;
+  uint32_t min_count, max_spread_q2;
 };
 
 // the block's slab: sum and sum2 as 64-bit words of n_cells each, then the counts
 __device__ __forceinline__ unsigned long long *slab_of(const GroundArgs &a, int block) {
-  return a.slabs + size_t(block) * (2u * size_t(a.n_cells) + (size_t(a.n_cells) + 1u) / 2u);   // (GroundPlan::block_bytes, in 64-bit words)
+  return a.slabs + size_t(block) * (2u * size_t(a.grid.n_cells) + (size_t(a.grid.n_cells) + 1u) / 2u);   // (GroundPlan::block_bytes, in 64-bit words)
 }
 
-// the sum over the wave's 64 lanes, in every lane; all 64 lanes are active at every call (the callers' control flow is
-// uniform).  row_shr 1, 2, 4, 8 scan a row of 16 (a lane with no source adds 0); row_bcast:15 / :31 carry the rows' totals
-// on: lane 63 holds all
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#define D2PC_GROUND_DPP_ADD(ctrl, rows) v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), ctrl, rows, 0xf, false))
-  D2PC_GROUND_DPP_ADD(0x111, 0xf);
-  D2PC_GROUND_DPP_ADD(0x112, 0xf);
-  D2PC_GROUND_DPP_ADD(0x114, 0xf);
-  D2PC_GROUND_DPP_ADD(0x118, 0xf);
-  D2PC_GROUND_DPP_ADD(0x142, 0xa);
-  D2PC_GROUND_DPP_ADD(0x143, 0xc);
-#undef D2PC_GROUND_DPP_ADD
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
-
-// one record slot of the wave into the block's table; k is the height in quanta, |k| <= 32767
+// one record of a lane into the block's table: the lane's own three LDS adds; k is the height in quanta, |k| <= 32767
 __device__ __forceinline__ void merge(unsigned long long *sum, unsigned long long *sum2, uint32_t *cnt, uint32_t cell, int k) {
-  bool live = cell != kNoCell;
-  [[maybe_unused]] const uint32_t lane = __lane_id();
-  const uint32_t k2 = uint32_t(k * k);   // < 2^30
-#pragma unroll
-  for (int round = 0; round < kGroundWaveRounds; ++round) {
-    const unsigned long long any = __ballot(live);
-    if (any == 0) break;
-    const int leader = __ffsll(any) - 1;
-    const uint32_t elected = uint32_t(__builtin_amdgcn_readlane(int(cell), leader));
-    const bool mine = live && cell == elected;
-    const uint32_t n = uint32_t(__popcll(__ballot(mine)));
-    const int s = int(wave_sum(mine ? uint32_t(k) : 0u));            // |the sum| <= 64 x 32767
-    const uint32_t lo = wave_sum(mine ? k2 & 0xFFFFu : 0u);          // <= 64 x 65535
-    const uint32_t hi = wave_sum(mine ? k2 >> 16 : 0u);              // <= 64 x 2^14
-    if (lane == uint32_t(leader)) {
-      atomicAdd(&sum[elected], static_cast<unsigned long long>(static_cast<long long>(s)));
-      atomicAdd(&sum2[elected], (static_cast<unsigned long long>(hi) << 16) + lo);
-      atomicAdd(&cnt[elected], n);
-    }
-    live = live && !mine;
-  }
-  if (live) {
-    atomicAdd(&sum[cell], static_cast<unsigned long long>(static_cast<long long>(k)));
-    atomicAdd(&sum2[cell], static_cast<unsigned long long>(k2));
-    atomicAdd(&cnt[cell], 1u);
-  }
+  if (cell == kNone) return;
+  atomicAdd(&sum[cell], static_cast<unsigned long long>(static_cast<long long>(k)));
+  atomicAdd(&sum2[cell], static_cast<unsigned long long>(uint32_t(k * k)));   // < 2^30
+  atomicAdd(&cnt[cell], 1u);
 }
 
 __device__ __forceinline__ float pick(int axis, uint32_t flip, float x, float y, float z) {
@@ -128,42 +70,24 @@ __global__ __launch_bounds__(kThreads) void k_ground_reduce(const GroundArgs a) 
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char lds[];
   unsigned long long *sum = reinterpret_cast<unsigned long long *>(lds);
-  unsigned long long *sum2 = sum + a.n_cells;
-  uint32_t *cnt = reinterpret_cast<uint32_t *>(sum2 + a.n_cells);
+  unsigned long long *sum2 = sum + a.grid.n_cells;
+  uint32_t *cnt = reinterpret_cast<uint32_t *>(sum2 + a.grid.n_cells);
   const uint32_t tid = threadIdx.x;
-  for (int i = int(tid); i < a.n_cells; i += kThreads) sum[i] = 0ull, sum2[i] = 0ull, cnt[i] = 0u;
+  for (int i = int(tid); i < a.grid.n_cells; i += kThreads) sum[i] = 0ull, sum2[i] = 0ull, cnt[i] = 0u;
   // the step: the same 15 words in every lane
   const float r0 = a.step[0], r1 = a.step[1], r2 = a.step[2], r3 = a.step[3], r4 = a.step[4], r5 = a.step[5], r6 = a.step[6],
               r7 = a.step[7], r8 = a.step[8], tx = a.step[9], ty = a.step[10], tz = a.step[11], a0 = a.step[12], b0 = a.step[13],
               h0 = a.step[14];
-  const float na = float(a.n_a), nb = float(a.n_b);
+  const float na = float(a.grid.n_a), nb = float(a.grid.n_b);
   __syncthreads();
 
-  for (uint64_t share = blockIdx.x; share < a.shares; share += uint64_t(a.blocks)) {
-    uint64_t cloud = 0;
-    uint32_t in_cloud = uint32_t(share);
-    if (a.n_clouds > 1) {
-      cloud = share / a.shares_per_cloud;
-      in_cloud = uint32_t(share - cloud * a.shares_per_cloud);
-    }
-    uint32_t n = a.cloud_points;
-    if (a.counts) {
-      const uint32_t given = a.counts[cloud];
-      n = given == 0xFFFFFFFFu ? 0u : min(given, a.cloud_points);
-    }
-    const uint32_t i0 = in_cloud * uint32_t(D2PC_SECTORS_SHARE_POINTS);   // (< 2^32: shares_per_cloud <= 2^22)
-    if (i0 >= n) continue;
-    const uint64_t first = cloud * a.stride;   // the cloud's first record in `points`
+  for (uint64_t share = blockIdx.x; share < a.walk.shares; share += uint64_t(a.blocks)) {
+    ShareAt at;
+    if (!find_share(a.walk, share, &at)) continue;   // (d2pc_sectors_device.hpp)
     uint4 rec[kPerLane];
     bool have[kPerLane];
 #pragma unroll
-    for (int k = 0; k < kPerLane; ++k) {
-      const uint32_t i = i0 + uint32_t(k * kThreads) + tid;   // (i0 + 1,023 <= 2^32 - 1: no wrap)
-      have[k] = i < n;
-      rec[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (have[k]) rec[k] = a.points[(first + i) * a.step16];
-      asm volatile("" ::"v"(rec[k].w));   // keeps the load a whole 16-byte one (w is not used: it would shrink to 12)
-    }
+    for (int k = 0; k < kPerLane; ++k) rec[k] = share_record(a.walk, at, tid, k, &have[k]);
     uint32_t cell[kPerLane];
     int q[kPerLane];
 #pragma unroll
@@ -179,7 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_ground_reduce(const GroundArgs a) 
       const float va = (pa - a0) * a.inv_c, vb = (pb - b0) * a.inv_c, v = (ph - h0) * a.inv_q;
       const bool part = have[k] && finite && va >= 0.0f && va < na && vb >= 0.0f && vb < nb && v >= -32767.0f && v <= 32767.0f;
       const int ia = int(floorf(va)), ib = int(floorf(vb));
-      cell[k] = part ? uint32_t(ib * a.n_a + ia) : kNoCell;
+      cell[k] = part ? uint32_t(ib * a.grid.n_a + ia) : kNone;
       q[k] = part ? int(rintf(v)) : 0;
     }
 #pragma unroll
@@ -188,8 +112,8 @@ __global__ __launch_bounds__(kThreads) void k_ground_reduce(const GroundArgs a) 
 
   __syncthreads();
   unsigned long long *slab = slab_of(a, int(blockIdx.x));
-  uint32_t *slab_c = reinterpret_cast<uint32_t *>(slab + 2 * size_t(a.n_cells));
-  for (int i = int(tid); i < a.n_cells; i += kThreads) slab[i] = sum[i], slab[a.n_cells + i] = sum2[i], slab_c[i] = cnt[i];
+  uint32_t *slab_c = reinterpret_cast<uint32_t *>(slab + 2 * size_t(a.grid.n_cells));
+  for (int i = int(tid); i < a.grid.n_cells; i += kThreads) slab[i] = sum[i], slab[a.grid.n_cells + i] = sum2[i], slab_c[i] = cnt[i];
 }
 
 __global__ __launch_bounds__(kThreads) void k_ground_merge(const GroundArgs a) {
@@ -197,7 +121,7 @@ __global__ __launch_bounds__(kThreads) void k_ground_merge(const GroundArgs a) {
   __shared__ uint32_t sc[kThreads];
   const int tid = int(threadIdx.x), slice = tid / kGroundMergeCells;
   const int cell = int(blockIdx.x) * kGroundMergeCells + tid % kGroundMergeCells;
-  const int n_cells = a.n_cells;
+  const int n_cells = a.grid.n_cells;
   unsigned long long sum = 0, sum2 = 0;
   uint32_t cnt = 0;
   if (cell < n_cells) {
@@ -233,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void k_ground_merge(const GroundArgs a) {
 __global__ __launch_bounds__(kGroundSiteThreads) void k_ground_sites(const GroundArgs a) {
   __shared__ GroundSiteLds lds;
   const int tid = int(threadIdx.x);
-  const int n_cells = a.n_cells;
+  const int n_cells = a.grid.n_cells;
   const uint8_t *flat_g = reinterpret_cast<const uint8_t *>(a.hand_on + 3 * size_t(n_cells));
   uint32_t points = 0, n_flat = 0;
   uint32_t spread[kGroundPerLane] = {};
@@ -247,8 +171,7 @@ __global__ __launch_bounds__(kGroundSiteThreads) void k_ground_sites(const Groun
     spread[k] = a.hand_on[2 * n_cells + c];
   }
   GroundSiteStage st;
-  st.n_a = a.n_a, st.n_b = a.n_b, st.n_cells = n_cells, st.window = a.window, st.n_candidates = a.n_candidates;
-  st.max_step_q = a.max_step_q, st.w_dist = a.w_dist, st.w_rough = a.w_rough, st.rough_cap = a.rough_cap;
+  st.grid = a.grid, st.n_candidates = a.n_candidates;
   st.goal_i = reinterpret_cast<const uint32_t *>(a.step)[15], st.goal_j = reinterpret_cast<const uint32_t *>(a.step)[16];
   st.allowed = a.allowed, st.site = a.site, st.candidates = a.candidates, st.summary = a.summary;
   ground_site_stage(st, lds, spread, points, n_flat);   // (d2pc_sectors_ground_sites.hpp: the terrain's site stage too)
@@ -264,23 +187,20 @@ int prepare_ground_kernels(const GroundPlan &p) {
 
 int launch_ground(const GroundLaunch &in) {
   GroundArgs a;
-  a.points = static_cast<const uint4 *>(in.points), a.counts = in.counts, a.step = static_cast<const float *>(in.step);
+  a.walk = in.walk, a.step = static_cast<const float *>(in.step);
   a.allowed = in.allowed;
   a.slabs = static_cast<unsigned long long *>(in.slabs), a.hand_on = static_cast<uint32_t *>(in.hand_on);
   a.count = in.count, a.sum = reinterpret_cast<unsigned long long *>(in.sum), a.sum2 = reinterpret_cast<unsigned long long *>(in.sum2);
   a.mean_q = reinterpret_cast<uint32_t *>(in.mean_q), a.spread_q2 = in.spread_q2, a.flat = in.flat, a.site = in.site;
   a.candidates = static_cast<unsigned long long *>(in.candidates), a.summary = in.summary;
   a.n_candidates = in.candidates ? in.n_candidates : 0;
-  a.stride = in.stride, a.shares = in.shares;
-  a.shares_per_cloud = in.shares_per_cloud, a.cloud_points = in.cloud_points, a.n_clouds = in.n_clouds, a.step16 = in.step16;
   a.blocks = in.blocks;
   const GroundPlan &p = in.plan;
-  a.n_a = p.n_a, a.n_b = p.n_b, a.n_cells = p.n_cells, a.window = p.window;
+  a.grid = ground_site_grid(p);
   a.axis_a = p.axis[0], a.axis_b = p.axis[1], a.axis_h = p.axis[2];
   a.flip_a = p.flip[0], a.flip_b = p.flip[1], a.flip_h = p.flip[2];
   a.inv_c = p.inv_c, a.inv_q = p.inv_q;
-  a.min_count = p.min_count, a.max_spread_q2 = p.max_spread_q2, a.max_step_q = p.max_step_q;
-  a.w_dist = p.w_dist, a.w_rough = p.w_rough, a.rough_cap = p.rough_cap;
+  a.min_count = p.min_count, a.max_spread_q2 = p.max_spread_q2;
   hipStream_t s = static_cast<hipStream_t>(in.stream);
   void *args[] = {&a};
   (void)hipLaunchKernel(reinterpret_cast<const void *>(&k_ground_reduce), dim3(unsigned(in.blocks)), dim3(kThreads), args, p.lds_bytes, s);

@@ -102,16 +102,12 @@ int d2pc_sectors_ground_process_device(d2pc_sectors_ground *g, const d2pc_sector
   if (!guard.ok) return fail(g->err, D2PC_ERR_NO_DEVICE, "cannot select device %d", g->device);
   GroundLaunch a;
   a.plan = g->plan;
-  a.points = d->points, a.counts = d->counts, a.step = d->step, a.allowed = d->allowed;
+  a.walk = cloud_walk(*d), a.step = d->step, a.allowed = d->allowed;
   a.slabs = g->d_slabs, a.hand_on = g->d_hand_on;
   a.count = d->count, a.sum = d->sum, a.sum2 = d->sum2, a.mean_q = d->mean_q, a.spread_q2 = d->spread_q2, a.flat = d->flat;
   a.site = d->site, a.candidates = d->candidates, a.summary = d->summary;
   a.n_candidates = d->candidates ? d->n_candidates : 0;
-  a.stride = d->n_clouds > 1 ? uint64_t(d->points_frame_stride_points) : 0;
-  a.cloud_points = uint32_t(d->cloud_points), a.n_clouds = uint32_t(d->n_clouds), a.step16 = uint32_t(d->point_step / 16);
-  a.shares_per_cloud = uint32_t((uint64_t(d->cloud_points) + D2PC_SECTORS_SHARE_POINTS - 1) / D2PC_SECTORS_SHARE_POINTS);
-  a.shares = uint64_t(a.shares_per_cloud) * uint64_t(a.n_clouds);
-  a.blocks = a.shares < uint64_t(g->blocks) ? int(a.shares) : g->blocks;   // (a block without a share would store an empty slab)
+  a.blocks = a.walk.shares < uint64_t(g->blocks) ? int(a.walk.shares) : g->blocks;   // (a block without a share would store an empty slab)
   a.stream = stream;   // NULL = HIP's default stream
   const hipError_t e = hipError_t(launch_ground(a));
   if (e != hipSuccess) return fail(g->err, D2PC_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));

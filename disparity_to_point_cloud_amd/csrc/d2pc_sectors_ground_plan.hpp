@@ -31,6 +31,19 @@ struct GroundPlan {
   int blocks_per_cu;
 };
 
+// what the site stage (d2pc_sectors_ground_sites.hpp) reads of a plan: the ground's and the terrain's kernel arguments embed it
+struct GroundSiteGrid {
+  int n_a, n_b, n_cells, window;
+  uint32_t max_step_q, w_dist, w_rough, rough_cap;
+};
+
+inline GroundSiteGrid ground_site_grid(const GroundPlan &p) {
+  GroundSiteGrid g;
+  g.n_a = p.n_a, g.n_b = p.n_b, g.n_cells = p.n_cells, g.window = p.window;
+  g.max_step_q = p.max_step_q, g.w_dist = p.w_dist, g.w_rough = p.w_rough, g.rough_cap = p.rough_cap;
+  return g;
+}
+
 // reducing blocks of a session on a device of `cus` compute units: one per kGroundSharesPerBlock shares of max_points,
 // 1 .. blocks_per_cu x cus; all of them for max_points 0
 inline int ground_blocks(uint32_t max_points, int blocks_per_cu, int cus) {
@@ -129,8 +142,7 @@ inline int check_ground_desc(const GroundPlan &p, const d2pc_sectors_ground_desc
 // One call as d2pc_sectors_ground.hip's kernels get it (d2pc_sectors_ground_capi.hip fills it).  The stream is a hipStream_t.
 struct GroundLaunch {
   GroundPlan plan;
-  const void *points;
-  const uint32_t *counts;
+  CloudWalk walk;
   const void *step;            // DEVICE: d2pc_sectors_ground_step
   const uint8_t *allowed;
   void *slabs;                 // DEVICE: the session's blocks x (sum, sum2, count of n_cells each)
@@ -144,9 +156,6 @@ struct GroundLaunch {
   void *candidates;
   uint32_t *summary;
   int n_candidates;            // 0 without candidates
-  uint64_t stride;             // records between the clouds; 0 for one cloud
-  uint64_t shares;             // n_clouds * shares_per_cloud
-  uint32_t shares_per_cloud, cloud_points, n_clouds, step16;
   int blocks;                  // of this launch: min(the session's, shares)
   void *stream;
 };

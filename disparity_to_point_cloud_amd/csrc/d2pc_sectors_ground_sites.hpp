@@ -6,30 +6,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "d2pc_sectors_device.hpp"
 #include "d2pc_sectors_ground_plan.hpp"
 
 namespace d2pc {
 namespace sectors {
-
-constexpr unsigned long long kGroundNoKey = ~0ull;
-
-// the wave's minimum of a 32-bit word in every lane (d2pc_sectors_steer.hip's, copied: the steer shares no code with the
-// ground); all 64 lanes are active at every call
-__device__ __forceinline__ uint32_t ground_wave_umin(uint32_t v) {
-#define D2PC_GROUND_DPP_MIN(ctrl, rows)                                                             \
-  {                                                                                                 \
-    const uint32_t o = uint32_t(__builtin_amdgcn_update_dpp(-1, int(v), ctrl, rows, 0xf, false));   \
-    v = o < v ? o : v;                                                                              \
-  }
-  D2PC_GROUND_DPP_MIN(0x111, 0xf)
-  D2PC_GROUND_DPP_MIN(0x112, 0xf)
-  D2PC_GROUND_DPP_MIN(0x114, 0xf)
-  D2PC_GROUND_DPP_MIN(0x118, 0xf)
-  D2PC_GROUND_DPP_MIN(0x142, 0xa)
-  D2PC_GROUND_DPP_MIN(0x143, 0xc)
-#undef D2PC_GROUND_DPP_MIN
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
 
 // mean_q (as a uint32) and spread_q2 of a cell from its count, sum and sum2: floor division towards -inf, S in wrapping
 // 64-bit arithmetic (exact for what ground calls accumulate); the empty cell's words for a count of 0
@@ -48,8 +29,8 @@ __device__ __forceinline__ void ground_cell_formula(uint32_t cnt, unsigned long 
 }
 
 struct GroundSiteStage {   // what the site stage reads of a call beside the block's LDS
-  int n_a, n_b, n_cells, window, n_candidates;   // n_candidates: 0 without candidates
-  uint32_t max_step_q, w_dist, w_rough, rough_cap;
+  GroundSiteGrid grid;
+  int n_candidates;   // 0 without candidates
   uint32_t goal_i, goal_j;
   const uint8_t *allowed;
   uint8_t *site;
@@ -71,8 +52,8 @@ struct GroundSiteLds {
 __device__ __forceinline__ void ground_site_stage(const GroundSiteStage &a, GroundSiteLds &lds, const uint32_t (&spread)[kGroundPerLane],
                                                   uint32_t points, uint32_t n_flat) {
   const int tid = int(threadIdx.x), lane = tid & 63, wave = tid >> 6;
-  const int n_cells = a.n_cells, n_a = a.n_a, n_b = a.n_b, W = a.window;
-  if (tid < D2PC_SECTORS_GROUND_MAX_CANDIDATES) lds.winner[tid] = kGroundNoKey;
+  const int n_cells = a.grid.n_cells, n_a = a.grid.n_a, n_b = a.grid.n_b, W = a.grid.window;
+  if (tid < D2PC_SECTORS_GROUND_MAX_CANDIDATES) lds.winner[tid] = kNoKey;
   const bool measured = a.goal_i < uint32_t(n_a) && a.goal_j < uint32_t(n_b);
   uint32_t n_sites = 0;
   __syncthreads();
@@ -80,13 +61,13 @@ __device__ __forceinline__ void ground_site_stage(const GroundSiteStage &a, Grou
   unsigned long long key[kGroundPerLane];
 #pragma unroll
   for (int k = 0; k < kGroundPerLane; ++k) {
-    key[k] = kGroundNoKey;
+    key[k] = kNoKey;
     const int c = tid + k * kGroundSiteThreads;
     if (c >= n_cells) continue;
     const int j = c / n_a, i = c - j * n_a;
     bool site = i - W >= 0 && i + W < n_a && j - W >= 0 && j + W < n_b && lds.flat[c] != 0 && (!a.allowed || a.allowed[c] != 0);
     if (site) {
-      const int m = lds.mean_q[c], step = int(a.max_step_q);
+      const int m = lds.mean_q[c], step = int(a.grid.max_step_q);
       for (int dj = -W; dj <= W; ++dj)
         for (int di = -W; di <= W; ++di) {
           const int o = c + dj * n_a + di;
@@ -101,7 +82,7 @@ __device__ __forceinline__ void ground_site_stage(const GroundSiteStage &a, Grou
     if (site) {
       const int di = i - int(a.goal_i), dj = j - int(a.goal_j);
       const uint32_t dist = measured ? uint32_t(di * di + dj * dj) : 0u;
-      const uint32_t cost = a.w_dist * dist + a.w_rough * (spread[k] < a.rough_cap ? spread[k] : a.rough_cap);
+      const uint32_t cost = a.grid.w_dist * dist + a.grid.w_rough * (spread[k] < a.grid.rough_cap ? spread[k] : a.grid.rough_cap);
       key[k] = (static_cast<unsigned long long>(cost) << 32) | uint32_t(c);
       ++n_sites;
     }
@@ -124,28 +105,8 @@ __device__ __forceinline__ void ground_site_stage(const GroundSiteStage &a, Grou
     }
   }
 
-  // ---- the K smallest keys, ascending (the steer's rounds)
-  unsigned long long head = key[0];   // the lane's smallest key not yet chosen
-#pragma unroll
-  for (int k = 1; k < kGroundPerLane; ++k) head = key[k] < head ? key[k] : head;
-  for (int r = 0; r < a.n_candidates; ++r) {
-    const uint32_t head_cost = uint32_t(head >> 32), head_cell = uint32_t(head);   // (all ones for no key: no cost is)
-    const uint32_t least = ground_wave_umin(head_cost);
-    const uint32_t cell = ground_wave_umin(head_cost == least ? head_cell : 0xFFFFFFFFu);
-    if (lane == 0 && least != 0xFFFFFFFFu) atomicMin(&lds.winner[r], (static_cast<unsigned long long>(least) << 32) | cell);
-    __syncthreads();
-    const unsigned long long best = lds.winner[r];   // (the same value in every lane)
-    if (best == kGroundNoKey) {   // no site is left: all ones from here on
-      if (tid < a.n_candidates - r) a.candidates[r + tid] = kGroundNoKey;
-      break;
-    }
-    if (tid == 0) a.candidates[r] = best;
-    if (head == best) {   // one lane of the block: its next key
-      head = kGroundNoKey;
-#pragma unroll
-      for (int k = 0; k < kGroundPerLane; ++k) head = key[k] > best && key[k] < head ? key[k] : head;
-    }
-  }
+  // ---- the K smallest keys, ascending (the steer's rounds: d2pc_sectors_device.hpp)
+  smallest_keys(key, a.n_candidates, lds.winner, a.candidates);
 }
 
 }  // namespace sectors

@@ -164,6 +164,28 @@ inline uint64_t position_bound(const Desc &d) {
   return uint64_t(d.n_clouds - 1) * stride + uint64_t(d.cloud_points);
 }
 
+// The records of a call as shares of D2PC_SECTORS_SHARE_POINTS records of one cloud each: what the reducing kernels of the
+// grid and of the ground walk (load_share, d2pc_sectors_device.hpp), and what their launches and kernel arguments embed
+struct CloudWalk {
+  const void *points;
+  const uint32_t *counts;
+  uint64_t stride;             // records between the clouds; 0 for one cloud
+  uint64_t shares;             // n_clouds * shares_per_cloud
+  uint32_t shares_per_cloud, cloud_points, n_clouds, step16;  // step16: 16-byte units of a record
+};
+
+// the walk over the cloud of a checked descriptor of either kind
+template <class Desc>
+inline CloudWalk cloud_walk(const Desc &d) {
+  CloudWalk w;
+  w.points = d.points, w.counts = d.counts;
+  w.stride = d.n_clouds > 1 ? uint64_t(d.points_frame_stride_points) : 0;
+  w.cloud_points = uint32_t(d.cloud_points), w.n_clouds = uint32_t(d.n_clouds), w.step16 = uint32_t(d.point_step / 16);
+  w.shares_per_cloud = uint32_t((uint64_t(d.cloud_points) + D2PC_SECTORS_SHARE_POINTS - 1) / D2PC_SECTORS_SHARE_POINTS);
+  w.shares = uint64_t(w.shares_per_cloud) * uint64_t(w.n_clouds);
+  return w;
+}
+
 // what d2pc_sectors_process_device refuses of a descriptor, for a session of plan `p`
 inline int check_desc(const Plan &p, const d2pc_sectors_desc *d, char *msg = nullptr, size_t msg_len = 0) {
   if (!d || d->struct_size != sizeof(d2pc_sectors_desc)) D2PC_SECTORS_REFUSE(D2PC_ERR_INVALID_ARG, "bad d2pc_sectors_desc");
@@ -191,17 +213,13 @@ inline int check_desc(const Plan &p, const d2pc_sectors_desc *d, char *msg = nul
 // One call as d2pc_sectors.hip's kernels get it (d2pc_sectors_capi.hip fills it).  The stream is a hipStream_t.
 struct Launch {
   Plan plan;
-  const void *points;
-  const uint32_t *counts;
+  CloudWalk walk;
   const float *table;          // DEVICE: half x (c, s), then plan.elev x (ce, se)
   uint64_t *slab_keys;         // DEVICE: blocks x n_cells
   uint32_t *slab_counts;       // DEVICE: blocks x n_cells
   float *range;
   uint32_t *count, *nearest;
   uint16_t *distance_cm;
-  uint64_t stride;             // records between the clouds; 0 for one cloud
-  uint64_t shares;             // n_clouds * shares_per_cloud
-  uint32_t shares_per_cloud, cloud_points, n_clouds, step16;  // step16: 16-byte units of a record
   int blocks;
   void *stream;
 };

@@ -13,17 +13,13 @@
 //                    among the lanes that hold it, of the cells -- two 32-bit minima over DPP row shifts and broadcasts,
 //                    no LDS -- and one lane issues one 64-bit LDS min into the round's own word (K words, preset to all
 //                    ones: nothing to reset, no word is used twice).  Behind the barrier every lane reads that word; the
-//                    one lane whose key it is looks for its next.
+//                    one lane whose key it is looks for its next.  The rounds are smallest_keys of
+//                    d2pc_sectors_device.hpp, which the ground's and the terrain's sites call too.
 //                    Vector stores only: no global atomic, nothing to clear.  Every value is an integer.
-// D2PC_SECTORS_STEER_FORM=0 builds the form that lost the A/B (tools/sectors_bench.py --steer --parent NAME): 64-bit
-// butterflies through ds_bpermute, one word per wave, and every wave merging the 16 words itself.
 #include <hip/hip_runtime.h>
 
+#include "d2pc_sectors_device.hpp"
 #include "d2pc_sectors_steer_plan.hpp"
-
-#ifndef D2PC_SECTORS_STEER_FORM
-#define D2PC_SECTORS_STEER_FORM 1
-#endif
 
 namespace d2pc {
 namespace sectors {
@@ -43,19 +39,6 @@ struct SteerArgs {   // SteerLaunch without its host-only members
   uint32_t free_cm, min_clearance_cm, horizon_cm, w_goal, w_prev, w_near;
 };
 
-constexpr unsigned long long kNoKey = ~0ull;
-
-#if !D2PC_SECTORS_STEER_FORM
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = __shfl_xor(v, m, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-#endif
-
 __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
@@ -64,27 +47,6 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
   }
   return v;
 }
-
-// The wave's minimum of a 32-bit word in every lane, without LDS: an inclusive scan along each row of 16 lanes (row_shr 1,
-// 2, 4, 8; a lane with no source keeps all ones), lane 15 of rows 0 and 2 broadcast into rows 1 and 3, lane 31 into rows 2
-// and 3; lane 63 then holds the minimum.  All 64 lanes must be active.
-#if D2PC_SECTORS_STEER_FORM
-__device__ __forceinline__ uint32_t wave_umin_dpp(uint32_t v) {
-#define D2PC_STEER_DPP_MIN(ctrl, rows)                                                              \
-  {                                                                                                 \
-    const uint32_t o = uint32_t(__builtin_amdgcn_update_dpp(-1, int(v), ctrl, rows, 0xf, false));   \
-    v = o < v ? o : v;                                                                              \
-  }
-  D2PC_STEER_DPP_MIN(0x111, 0xf)   // row_shr:1
-  D2PC_STEER_DPP_MIN(0x112, 0xf)   // row_shr:2
-  D2PC_STEER_DPP_MIN(0x114, 0xf)   // row_shr:4
-  D2PC_STEER_DPP_MIN(0x118, 0xf)   // row_shr:8
-  D2PC_STEER_DPP_MIN(0x142, 0xa)   // row_bcast:15 into rows 1 and 3
-  D2PC_STEER_DPP_MIN(0x143, 0xc)   // row_bcast:31 into rows 2 and 3
-#undef D2PC_STEER_DPP_MIN
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
-}
-#endif
 
 // D of the specification, times w; 0 when the sector switches the term off
 __device__ __forceinline__ uint32_t turn_cost(uint32_t w, int s, int l, uint32_t to_sector, uint32_t to_layer, int n, int layers) {
@@ -97,12 +59,8 @@ __device__ __forceinline__ uint32_t turn_cost(uint32_t w, int s, int l, uint32_t
 
 __global__ __launch_bounds__(kSteerThreads) void k_sectors_steer(const SteerArgs a) {
   extern __shared__ __align__(16) unsigned char lds[];
-#if D2PC_SECTORS_STEER_FORM
   __shared__ unsigned long long winner[D2PC_SECTORS_STEER_MAX_CANDIDATES];   // round r's own word
-  if (threadIdx.x < D2PC_SECTORS_STEER_MAX_CANDIDATES) winner[threadIdx.x] = ~0ull;   // (two barriers lie before the first min into it)
-#else
-  __shared__ unsigned long long slot[2][kSteerWaves];
-#endif
+  if (threadIdx.x < D2PC_SECTORS_STEER_MAX_CANDIDATES) winner[threadIdx.x] = kNoKey;   // (two barriers lie before the first min into it)
   __shared__ uint32_t free_slot[kSteerWaves], near_slot[kSteerWaves];
   uint16_t *plane_d = reinterpret_cast<uint16_t *>(lds);       // d, after the free_cm mapping
   uint16_t *plane_a = plane_d + a.n_cells;                     // the azimuth pass's minima
@@ -193,51 +151,7 @@ __global__ __launch_bounds__(kSteerThreads) void k_sectors_steer(const SteerArgs
   }
 
   // ---- (5) the K smallest keys, ascending
-#if D2PC_SECTORS_STEER_FORM
-  unsigned long long head = key[0];   // the lane's smallest key not yet chosen
-#pragma unroll
-  for (int k = 1; k < kSteerPerLane; ++k) head = key[k] < head ? key[k] : head;
-  for (int r = 0; r < a.n_candidates; ++r) {
-    const uint32_t head_cost = uint32_t(head >> 32), head_cell = uint32_t(head);   // (all ones for no key: no cost is)
-    const uint32_t least = wave_umin_dpp(head_cost);
-    const uint32_t cell = wave_umin_dpp(head_cost == least ? head_cell : 0xFFFFFFFFu);
-    if (lane == 0 && least != 0xFFFFFFFFu) atomicMin(&winner[r], (static_cast<unsigned long long>(least) << 32) | cell);
-    __syncthreads();
-    const unsigned long long best = winner[r];   // (the same value in every lane)
-    if (best == kNoKey) {   // no free cell is left: all ones from here on
-      if (tid < a.n_candidates - r) a.candidates[r + tid] = kNoKey;
-      break;
-    }
-    if (tid == 0) a.candidates[r] = best;
-    if (head == best) {   // one lane of the block: its next key
-      head = kNoKey;
-#pragma unroll
-      for (int k = 0; k < kSteerPerLane; ++k) head = key[k] > best && key[k] < head ? key[k] : head;
-    }
-  }
-#else
-  unsigned long long bound = 0;
-  for (int r = 0; r < a.n_candidates; ++r) {
-    unsigned long long best = kNoKey;
-#pragma unroll
-    for (int k = 0; k < kSteerPerLane; ++k) best = key[k] >= bound && key[k] < best ? key[k] : best;
-    best = wave_min(best);
-    if (lane == 0) slot[r & 1][wave] = best;
-    __syncthreads();   // (the row of round r + 2 is written behind the barrier of round r + 1: every wave has read this one by then)
-    best = slot[r & 1][0];
-#pragma unroll
-    for (int w = 1; w < kSteerWaves; ++w) {
-      const unsigned long long o = slot[r & 1][w];
-      best = o < best ? o : best;
-    }
-    if (best == kNoKey) {   // (the same value in every lane) no free cell is left: all ones from here on
-      if (tid < a.n_candidates - r) a.candidates[r + tid] = kNoKey;
-      break;
-    }
-    if (tid == 0) a.candidates[r] = best;
-    bound = best + 1;
-  }
-#endif
+  smallest_keys(key, a.n_candidates, winner, a.candidates);   // (d2pc_sectors_device.hpp)
 }
 
 }  // namespace

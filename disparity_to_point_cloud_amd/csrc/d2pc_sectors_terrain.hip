@@ -45,9 +45,9 @@ struct TerrainArgs {   // TerrainLaunch without its host-only members
   unsigned long long *candidates;
   uint32_t *summary, *status;
   int depth, n_candidates;
-  int n_a, n_b, n_cells, window;
+  GroundSiteGrid grid;
   float inv_c;
-  uint32_t min_count, max_spread_q2, max_step_q, w_dist, w_rough, rough_cap;
+  uint32_t min_count, max_spread_q2;
 };
 
 __device__ __forceinline__ unsigned long long *table_of(const TerrainArgs &a, int slot) {
@@ -60,7 +60,7 @@ __device__ __forceinline__ unsigned long long *table_of(const TerrainArgs &a, in
 // zero -- so they are in flight together.
 __device__ __forceinline__ void add_stored(const TerrainArgs &a, const int *part_slot, const int *part_di, const int *part_dj, int n_part, int c,
                                            int i, int j, uint32_t &cnt, unsigned long long &sum, unsigned long long &sum2) {
-  const int n_a = a.n_a, n_b = a.n_b, n_cells = a.n_cells;
+  const int n_a = a.grid.n_a, n_b = a.grid.n_b, n_cells = a.grid.n_cells;
   for (int p0 = 0; p0 < n_part; p0 += kTerrainBatch) {
     unsigned long long s1[kTerrainBatch], s2[kTerrainBatch];
     uint32_t sc[kTerrainBatch];
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(kGroundSiteThreads) void k_terrain_update(const Ter
   __shared__ int part_slot[D2PC_SECTORS_TERRAIN_MAX_DEPTH], part_di[D2PC_SECTORS_TERRAIN_MAX_DEPTH], part_dj[D2PC_SECTORS_TERRAIN_MAX_DEPTH];
   __shared__ int part_n;
   const int tid = int(threadIdx.x);
-  const int n_cells = a.n_cells, n_a = a.n_a, n_b = a.n_b, depth = a.depth;
+  const int n_cells = a.grid.n_cells, n_a = a.grid.n_a, n_b = a.grid.n_b, depth = a.depth;
   if (tid < depth) hdr[tid] = a.headers[tid];
   // ---- 1. the anchor: the same words in every lane
   const uint32_t h0_bits = a.step[14];
@@ -175,8 +175,7 @@ __global__ __launch_bounds__(kGroundSiteThreads) void k_terrain_update(const Ter
   }
   if (!(a.site || a.candidates || a.summary)) return;   // (uniform: kernel arguments)
   GroundSiteStage st;
-  st.n_a = n_a, st.n_b = n_b, st.n_cells = n_cells, st.window = a.window, st.n_candidates = a.n_candidates;
-  st.max_step_q = a.max_step_q, st.w_dist = a.w_dist, st.w_rough = a.w_rough, st.rough_cap = a.rough_cap;
+  st.grid = a.grid, st.n_candidates = a.n_candidates;
   st.goal_i = a.step[15], st.goal_j = a.step[16];
   st.allowed = a.allowed, st.site = a.site, st.candidates = a.candidates, st.summary = a.summary;
   ground_site_stage(st, lds, spread, points, n_flat);
@@ -201,10 +200,8 @@ int launch_terrain(const TerrainLaunch &in) {
   a.candidates = static_cast<unsigned long long *>(in.candidates), a.summary = in.summary, a.status = in.status;
   a.depth = in.plan.depth, a.n_candidates = in.candidates ? in.n_candidates : 0;
   const GroundPlan &p = in.plan.ground;
-  a.n_a = p.n_a, a.n_b = p.n_b, a.n_cells = p.n_cells, a.window = p.window;
-  a.inv_c = p.inv_c;
-  a.min_count = p.min_count, a.max_spread_q2 = p.max_spread_q2, a.max_step_q = p.max_step_q;
-  a.w_dist = p.w_dist, a.w_rough = p.w_rough, a.rough_cap = p.rough_cap;
+  a.grid = ground_site_grid(p), a.inv_c = p.inv_c;
+  a.min_count = p.min_count, a.max_spread_q2 = p.max_spread_q2;
   hipLaunchKernelGGL(k_terrain_update, dim3(1), dim3(kGroundSiteThreads), 0, static_cast<hipStream_t>(in.stream), a);
   return int(hipGetLastError());
 }

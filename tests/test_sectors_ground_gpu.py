@@ -360,6 +360,21 @@ def test_the_largest_grid_more_cells_than_the_sites_block_has_lanes():
     assert r["summary"].tolist() == [256, 256, 0, 0] and np.all(r["candidates"] == NONE)
 
 
+@pytest.mark.parametrize("goal", [(2, 50), (OFF, OFF)], ids=["goal-on-the-last", "goal-off"])
+def test_one_lane_of_the_sites_block_holds_every_winner_in_a_row(goal):
+    """The only allowed cells are (2, 2), (2, 18), (2, 34) and (2, 50): 130, 1,154, 2,178 and 3,202, which lane 130 of the
+    sites' block holds in its slots 0 .. 3 (W = 2: i = 2 is no border cell), so one lane wins round after round and looks
+    for its next key each time; with the goal on the last of them its best key sits in its last slot."""
+    h = built(**GRIDS["64x64"])
+    heights = [[(i * 7 + j * 3) % 5 for i in range(64)] for j in range(64)]
+    cells = [130, 1154, 2178, 3202]
+    allowed = np.zeros(4096, dtype=np.uint8)
+    allowed[cells] = 1
+    r = h.run(cloud_of_cells(h, heights), gref.step_words(EYE, ZERO, ZERO, *goal), allowed=allowed, k=5, what="goal %s" % (goal,))
+    got = [int(c) & 0xFFFFFFFF for c in r["candidates"][:4]]
+    assert got == (cells[::-1] if goal[0] != OFF else cells) and r["candidates"][4] == NONE and r["summary"][2] == 4
+
+
 # ------------------------------------------------------------------------------------------------ the outputs
 def test_outputs_alone_and_together_and_refusals_enqueue_nothing():
     h = harness()

@@ -394,6 +394,22 @@ def test_candidates_over_the_whole_block():
     assert 0 < r["summary"][0] < 5760 and np.all(np.diff(r["candidates"].astype(np.float64)) > 0) and (r["clearance_cm"] < d).any()
 
 
+def test_one_lane_holds_every_winner_in_a_row():
+    """The only free cells are 7, 1,031, 2,055 and 3,079: lane 7 of the block holds all four, in its slots 0 .. 3, so the
+    same lane wins round after round and looks for its next key each time.  Without a goal every cost is equal and the
+    candidates come in slot order; with the goal on the last of them the lane's best key sits in its last slot."""
+    h = harness("90x64e", w_prev=0, w_near=0, min_clearance_cm=0)
+    d = h.empty()
+    cells = [7, 1031, 2055, 3079]
+    only = np.zeros(5760, dtype=np.uint8)
+    only[cells] = 1
+    r = h.run(d, allowed=only, k=5, what="four free cells of one lane, one cost")
+    assert r["candidates"].tolist() == [key_of(0, c) for c in cells] + [NONE] and r["summary"][0] == 4
+    r = h.run(d, step=sref.step_words(3079 % 90, 3079 // 90), allowed=only, k=5, what="four free cells of one lane, the goal on the last")
+    assert r["candidates"][0] == key_of(0, 3079) and r["candidates"][4] == NONE
+    assert sorted(int(c) & 0xFFFFFFFF for c in r["candidates"][:4]) == cells and np.all(np.diff(r["candidates"][:4].astype(np.float64)) > 0)
+
+
 @pytest.mark.parametrize("name", list(GRIDS))
 def test_random_grids(name):
     h = harness(name)

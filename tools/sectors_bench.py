@@ -35,9 +35,11 @@ ranks them).  GPU box only.
                                         ->  profiles/sectors_refactor_bench.txt: this build against libd2pc_sectors_NAME.so, a build
                                             of the parent commit's sources (`make sectors SNAME=NAME` there), when a change must move
                                             neither a byte nor the time: S of 72 x 1, 360 x 16 height, 72 x 16 and 60 x 30 elevation
-                                            and M of 72 x 1 and 60 x 30 elevation on the rig's merged cloud, the outputs of the two
-                                            builds compared bit for bit first, all twelve arms in ONE interleaved run; a row's new
-                                            median may exceed the parent's by no more than the arms' spread in that run
+                                            and M of 72 x 1 and 60 x 30 elevation on the rig's merged cloud, the steer's T and T32 of
+                                            72 x 1 and 60 x 30 elevation, the ground's G of 16 x 16 and 64 x 64 cells and the terrain's
+                                            update U of 16 x 16 x 8 and 64 x 64 x 16 on the rig's level ground, the outputs of the two
+                                            builds compared bit for bit first, all arms in ONE interleaved run; a row's new median may
+                                            exceed the parent's by no more than the arms' spread in that run
   python tools/sectors_bench.py --steer [--parent NAME]
                                         ->  profiles/sectors_steer_bench.txt: the steer (d2pc_sectors_steer_device, one launch of one
                                             block) behind the sectors and the memory: T = the steer alone (T32: 32 candidates), SMT =
@@ -45,17 +47,13 @@ ranks them).  GPU box only.
                                             one-camera frame and on the rig's merged cloud, for 72 x 1 and 60 x 30 elevation, in ONE
                                             interleaved run.  No time is fixed in advance: the yardsticks are S0 and M of the same run.
                                             With --parent NAME also T and T32 of libd2pc_sectors_NAME.so, another build of the steer's
-                                            kernel (`make sectors SNAME=butterfly SDEFS=-DD2PC_SECTORS_STEER_FORM=0`: the form of the
-                                            candidate rounds that lost), its outputs compared bit for bit with this build's first
+                                            kernel, its outputs compared bit for bit with this build's first
   python tools/sectors_bench.py --ground
                                         ->  profiles/sectors_ground_bench.txt: the landing grid (d2pc_sectors_ground_process_device, three
                                             launches) on a level ground under a camera that looks down: G = the call alone, G0 = with a
                                             count of 0 (the fixed part), C = the copy of the bytes G reads, S / S0 = the 72 x 1 sectors call
                                             on the same cloud, for 16 x 16 and 64 x 64 cells, the one-camera frame and the rig's merged
-                                            cloud, in producer order and shuffled, in ONE interleaved run.  Where libd2pc_sectors_gwave.so
-                                            and libd2pc_sectors_gplain.so are built (`make sectors SNAME=gwave
-                                            SDEFS=-DD2PC_SECTORS_GROUND_FORCE_ROUNDS=2`, `... SNAME=gplain ...=0`) the two forms of the
-                                            reduction stand beside it, their outputs compared bit for bit with the product's first
+                                            cloud, in producer order and shuffled, in ONE interleaved run
   python tools/sectors_bench.py --terrain
                                         ->  profiles/sectors_terrain_bench.txt: the terrain's update (d2pc_sectors_terrain_update_device,
                                             one launch of one block) alone on the ground call's tables, for 16 x 16 cells at depth 8 and
@@ -150,6 +148,54 @@ class Producer:
     def close(self):
         if self.rig is not None:
             self.rig.close()
+
+
+# ---- the inputs --steer, --ground, --terrain and --parent share
+HALF_PI = float(np.float32(np.pi / 2))
+HISTOGRAM = dict(n_sectors=60, n_layers=30, u_min=-HALF_PI, u_max=HALF_PI, azimuth0=-np.pi / 60, layer_kind=d2pc.LAYERS_ELEVATION)
+# (row, grid, the steer's reach)
+STEER_GRIDS = [("72 x 1", dict(), dict(max_reach_sectors=8, max_reach_layers=0)),
+               ("60 x 30 elevation", HISTOGRAM, dict(max_reach_sectors=8, max_reach_layers=4))]
+GROUND_GRIDS = [(dict(n_a=16, n_b=16, cell_size=0.5), 8), (dict(n_a=64, n_b=64, cell_size=0.125), 16)]   # (grid, the terrain's depth)
+NADIR = np.array([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]])
+
+
+def steer_outputs(n_cells, k):
+    return dict(clearance_cm=torch.empty(n_cells, dtype=torch.int16, device="cuda"), cost=torch.empty(n_cells, dtype=torch.int32, device="cuda"),
+                candidates=torch.empty(k, dtype=torch.int64, device="cuda"), summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+
+
+def ground_outputs(nc, k):
+    return dict(count=torch.empty(nc, dtype=torch.int32, device="cuda"), sum=torch.empty(nc, dtype=torch.int64, device="cuda"),
+                sum2=torch.empty(nc, dtype=torch.int64, device="cuda"), mean_q=torch.empty(nc, dtype=torch.int32, device="cuda"),
+                spread_q2=torch.empty(nc, dtype=torch.int32, device="cuda"), flat=torch.empty(nc, dtype=torch.uint8, device="cuda"),
+                site=torch.empty(nc, dtype=torch.uint8, device="cuda"), candidates=torch.empty(k, dtype=torch.int64, device="cuda"),
+                summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+
+
+def ground_grid(grid, prod):
+    """A ground configuration of the level-ground cloud: flat up to a standard deviation of 0.15 m, steps up to 100 quanta."""
+    return dict(grid, max_points=prod.cap, max_spread_q2=d2pc.sectors_ground_spread_of_std(0.002, 0.15), max_step_q=100)
+
+
+def level_ground(ctx, prod, gen, s):
+    """The producer's frames replaced by a level ground 5.4 m below a camera that looks straight down (its holes kept) and
+    run -> (records, the cloud, the grid's corner: 4 m to either side of camera 0's median record, h0 at its median height)."""
+    level = torch.randint(94, 99, tuple(prod.frames.shape), generator=gen, device="cuda", dtype=torch.int32).to(torch.uint8)
+    level[prod.frames == 0] = 0
+    prod.frames = level
+    prod(s)
+    torch.cuda.synchronize()
+    ctx.check_async_error()
+    npts = int(prod.offsets.cpu().numpy().view(np.uint32)[prod.n]) if prod.rig_case else int(prod.counts.cpu().numpy().view(np.uint32)[0])
+    cloud = prod.pts[:npts].clone()
+    mid = np.median(cloud[:min(npts, prod.roi_n // 2), :3].cpu().numpy().astype(np.float64) @ NADIR.T + [0.0, 0.0, 10.0], axis=0)
+    return npts, cloud, [np.round(mid[0]) - 4.0, np.round(mid[1]) - 4.0, float(np.float32(mid[2]))]   # a multiple of both cell sizes
+
+
+def ground_step(corner):
+    """The nadir pose and the grid's corner as a device step, the goal on cell (8, 8)."""
+    return torch.from_numpy(d2pc.sectors_ground_step(NADIR, [0.0, 0.0, 10.0], corner, 8, 8).view(np.int32).copy()).to("cuda")
 
 
 def bench(a):
@@ -348,24 +394,35 @@ def verdicts(t, rows):
     return lines
 
 
+def same_bytes(new, old):
+    """Whether two builds' outputs of one row hold the same bytes."""
+    bits = lambda x: x.view(torch.int32) if x.dtype == torch.float32 else x  # noqa: E731
+    return all(torch.equal(bits(new[k]), bits(old[k])) for k in new)
+
+
 def parent(a):
-    """This build against libd2pc_sectors_<parent>.so on the rig's merged cloud: S of four grids and M of two, the outputs
-    of the two builds compared bit for bit first, then all twelve arms interleaved in one run."""
+    """This build against libd2pc_sectors_<parent>.so: S of four grids and M of two on the rig's merged cloud, T and T32 of
+    two grids on the memory's distance_cm, G of two grids and the terrain's update U of two windows on the rig's level
+    ground; the outputs of the two builds of every row compared bit for bit first, then all arms interleaved in one run."""
     prop = torch.cuda.get_device_properties(0)
-    half_pi = float(np.float32(np.pi / 2))
-    histogram = dict(n_sectors=60, n_layers=30, u_min=-half_pi, u_max=half_pi, azimuth0=-np.pi / 60, layer_kind=d2pc.LAYERS_ELEVATION)
+    builds = (("new", None), ("parent", a.parent))
     s_rows = [("S 72 x 1 height", dict()), ("S 360 x 16 height", dict(n_sectors=360, n_layers=16, u_min=-40.0, u_max=40.0)),
-              ("S 72 x 16 elevation", dict(n_sectors=72, n_layers=16, u_min=-half_pi, u_max=half_pi, layer_kind=d2pc.LAYERS_ELEVATION)),
-              ("S 60 x 30 elevation", histogram)]
-    m_rows = [("M 72 x 1 height", dict()), ("M 60 x 30 elevation", histogram)]
+              ("S 72 x 16 elevation", dict(n_sectors=72, n_layers=16, u_min=-HALF_PI, u_max=HALF_PI, layer_kind=d2pc.LAYERS_ELEVATION)),
+              ("S 60 x 30 elevation", HISTOGRAM)]
+    m_rows = [("M 72 x 1 height", STEER_GRIDS[0]), ("M 60 x 30 elevation", STEER_GRIDS[1])]
     lines = ["# tools/sectors_bench.py --parent %s --rounds %d --iters %d" % (a.parent, a.rounds, a.iters),
              "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round)" % (
                  prop.name, prop.multi_processor_count),
              "# new = libd2pc_sectors.so, parent = libd2pc_sectors_%s.so (`make sectors SNAME=%s` of the parent commit's sources), on the" % (a.parent, a.parent),
              "# 16-camera rig's merged cloud.  S = d2pc_sectors_process_device alone (range + count); M = d2pc_sectors_memory_update_device",
              "# alone (range, distance_cm, age; a 37-degree yaw, a translation and dt 50 every call, max_age 2,000, a forward field of",
-             "# view as `covered`).  The two builds' outputs of every row were compared bit for bit before the timing.  us per call:",
-             "# median (min .. max).  new may be slower by no more than the larger of the two arms' (max - min) / median in this run"]
+             "# view as `covered`); T / T32 = d2pc_sectors_steer_device alone (reach 8 sectors and 0 / 4 layers, clearance_cm, cost, summary and",
+             "# 1 / 32 candidates) on the distance_cm M's row left behind its warm-up; G = d2pc_sectors_ground_process_device alone (three",
+             "# launches, all nine outputs, 32 candidates) on the rig's merged cloud of tools/sectors_bench.py --ground's level ground; U =",
+             "# d2pc_sectors_terrain_update_device alone (all nine outputs, 32 candidates, status) on the new G's count / sum / sum2 with the",
+             "# corner held: every slot of the window takes part.  The two builds' outputs of every row were compared bit for bit before the",
+             "# timing.  us per call: median (min .. max).  new may be slower by no more than the larger of the two arms' (max - min) / median",
+             "# in this run"]
     gen = torch.Generator(device="cuda").manual_seed(1)
     s = torch.cuda.current_stream().cuda_stream
     name, n, w, h, mode, rig_case, holes = CASES[1]
@@ -376,22 +433,29 @@ def parent(a):
         ctx.check_async_error()
         npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n])
         cloud = prod.pts[:npts].clone()
+        level_n, level_cloud, corner = level_ground(ctx, prod, gen, s)
+        g_rows = [(ground_grid(grid, prod), depth) for grid, depth in GROUND_GRIDS]
         prod.close()
     R = np.array([[np.cos(0.6458), 0.0, np.sin(0.6458)], [0.0, 1.0, 0.0], [-np.sin(0.6458), 0.0, np.cos(0.6458)]])   # about the optical y
     step = torch.from_numpy(d2pc.sectors_memory_step(R, [0.4, -0.1, 0.9], 50).view(np.int32).copy()).to("cuda")
     arms, labels, pairs, keep = [], [], [], []
+
+    def add(row, which, fn):
+        arms.append(fn)
+        labels.append("%s %s" % (row, which))
+
     for row, grid in s_rows:
         outs = []
-        for which, variant in (("new", None), ("parent", a.parent)):
+        for which, variant in builds:
             sec = d2pc.Sectors(variant=variant, **grid)
             out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
                        count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
             keep.append(sec)
             outs.append(out)
-            arms.append(lambda sec=sec, out=out: sec.process(cloud, npts, stream_ptr=s, **out))
-            labels.append("%s %s" % (row, which))
+            add(row, which, lambda sec=sec, out=out: sec.process(cloud, npts, stream_ptr=s, **out))
         pairs.append((row, outs))
-    for row, grid in m_rows:
+    memories = []
+    for row, (_, grid, reach) in m_rows:
         sec = d2pc.Sectors(**grid)
         seen = dict(count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
                     nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
@@ -399,27 +463,74 @@ def parent(a):
         cov = torch.from_numpy(d2pc.sectors_memory_coverage(sec.cfg, [(0.0, 0.0, 1.5, 1.0, 0.05)])).to("cuda")
         keep += [sec, seen, cov]
         outs = []
-        for which, variant in (("new", None), ("parent", a.parent)):
+        for which, variant in builds:
             mem = d2pc.SectorsMemory(sec.cfg, 2000, variant=variant)
             out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"),
                        distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"),
                        age=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
             keep.append(mem)
             outs.append(out)
-            arms.append(lambda mem=mem, seen=seen, cov=cov, out=out: mem.update(cloud, npts, seen["count"], seen["nearest"], step, covered=cov,
-                                                                                stream_ptr=s, **out))
-            labels.append("%s %s" % (row, which))
+            add(row, which, lambda mem=mem, seen=seen, cov=cov, out=out: mem.update(cloud, npts, seen["count"], seen["nearest"], step, covered=cov,
+                                                                                    stream_ptr=s, **out))
         pairs.append((row, outs))
+        memories.append((sec, outs[0]))
     for _ in range(3):   # warm-up: code objects; three updates, so that the memories carry, age and drop
         for fn in arms:
             fn()
         torch.cuda.synchronize()
         for row, (new, old) in pairs:   # (the memories of the two builds advance in step: the same number of calls)
-            assert all(torch.equal(new[k].view(torch.int32) if new[k].dtype == torch.float32 else new[k],
-                                   old[k].view(torch.int32) if old[k].dtype == torch.float32 else old[k]) for k in new), row + ": the builds disagree"
+            assert same_bytes(new, old), row + ": the builds disagree"
+    # ---- the one-block kernels and the ground: T on a copy of what M left (M goes on advancing), G and U on the level ground
+    first = len(arms)
+    for (gname, _, reach), (sec, left) in zip(STEER_GRIDS, memories):
+        dcm = left["distance_cm"].clone()
+        goal = torch.from_numpy(d2pc.sectors_steer_step(sec.cfg.n_sectors // 3, sec.cfg.n_layers // 2, 1, sec.cfg.n_layers // 2)
+                                .view(np.int32).copy()).to("cuda")
+        keep += [dcm, goal]
+        for tag, k in (("T", 1), ("T32", 32)):
+            row, outs = "%s %s" % (tag, gname), []
+            for which, variant in builds:
+                st = d2pc.SectorsSteer(sec.cfg, variant=variant, **reach)
+                out = steer_outputs(sec.n_cells, k)
+                keep.append(st)
+                outs.append(out)
+                add(row, which, lambda st=st, dcm=dcm, goal=goal, k=k, out=out: st.steer(dcm, goal, n_candidates=k, stream_ptr=s, **out))
+            pairs.append((row, outs))
+    gstep = ground_step(corner)
+    count = torch.tensor([level_n], dtype=torch.int32, device="cuda")
+    windows = []
+    for grid, depth in g_rows:
+        row, outs = "G %d x %d" % (grid["n_a"], grid["n_b"]), []
+        for which, variant in builds:
+            g = d2pc.SectorsGround(variant=variant, **grid)
+            out = ground_outputs(g.n_cells, 32)
+            keep.append(g)
+            outs.append(out)
+            add(row, which, lambda g=g, out=out: g.process(level_cloud, level_n, gstep, counts=count, n_candidates=32, stream_ptr=s, **out))
+        pairs.append((row, outs))
+        cfg, tables, nc = g.cfg, outs[0], g.n_cells
+        row, outs = "U %d x %d x %d" % (grid["n_a"], grid["n_b"], depth), []
+        for which, variant in builds:
+            ter = d2pc.SectorsTerrain(cfg, depth=depth, variant=variant)   # a window each
+            out, status = ground_outputs(nc, 32), torch.zeros(4, dtype=torch.int32, device="cuda")
+            keep.append(ter)
+            outs.append(dict(out, status=status))
+            add(row, which, lambda ter=ter, tables=tables, out=out, status=status: ter.update(gstep, tables["count"], tables["sum"], tables["sum2"],
+                                                                                              n_candidates=32, status=status, stream_ptr=s, **out))
+        pairs.append((row, outs))
+        windows.append((row, depth, outs[0]["status"]))
+    for _ in range(20):   # warm-up: code objects, and more updates than the deepest window holds
+        for fn in arms[first:]:
+            fn()
+    torch.cuda.synchronize()
+    for row, (new, old) in pairs[len(s_rows) + len(m_rows):]:
+        assert same_bytes(new, old), row + ": the builds disagree"
+    for row, depth, status in windows:
+        took = int(status.cpu().numpy().view(np.uint32)[1])
+        assert took == depth, "%s: %d slots took part" % (row, took)
     iters = int(min(max(a.iters, 30000.0 / timed(arms[0], 5)), 4000))   # (a sectors arm: no memory advances alone)
     t = dict(zip(labels, interleaved(arms, a.rounds, iters)))
-    lines.append("# %d points, %.1f MB read by S, %d calls per timed window" % (npts, 16 * npts / 1e6, iters))
+    lines.append("# %d points, %.1f MB read by S; %d records of the level ground read by G; %d calls per timed window" % (npts, 16 * npts / 1e6, level_n, iters))
     lines += verdicts(t, [row for row, _ in pairs])
     for x in keep:
         if hasattr(x, "close"):
@@ -514,10 +625,6 @@ def steer(a):
     """The steer call beside the sectors call and the memory's update it follows, all arms of all rows interleaved in one run."""
     import sectors_steer_ref
     prop = torch.cuda.get_device_properties(0)
-    half_pi = float(np.float32(np.pi / 2))
-    grids = [("72 x 1", dict(), dict(max_reach_sectors=8, max_reach_layers=0)),
-             ("60 x 30 elevation", dict(n_sectors=60, n_layers=30, u_min=-half_pi, u_max=half_pi, azimuth0=-np.pi / 60,
-                                        layer_kind=d2pc.LAYERS_ELEVATION), dict(max_reach_sectors=8, max_reach_layers=4))]
     lines = ["# tools/sectors_bench.py --steer%s --rounds %d --iters %d" % (" --parent " + a.parent if a.parent else "", a.rounds, a.iters),
              "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round)" % (
                  prop.name, prop.multi_processor_count),
@@ -544,7 +651,7 @@ def steer(a):
     arms, labels, rows, versus = [], [], [], []
     for cname, npts, cloud in clouds:
         zero = torch.zeros(1, dtype=torch.int32, device="cuda")
-        for gname, grid, reach in grids:
+        for gname, grid, reach in STEER_GRIDS:
             sec = d2pc.Sectors(**grid)
             mem = d2pc.SectorsMemory(sec.cfg, 2000)
             st = d2pc.SectorsSteer(sec.cfg, **reach)
@@ -555,9 +662,7 @@ def steer(a):
                       nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
             so0 = {k: torch.empty_like(v) for k, v in so.items()}   # S0's own: M reads a full cloud's count / nearest from `so`
             mo = dict(distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
-            to = dict(clearance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"),
-                      cost=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
-                      candidates=torch.empty(32, dtype=torch.int64, device="cuda"), summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+            to = steer_outputs(sec.n_cells, 32)
             keep.append((sec, mem, st, goal, cov, so, so0, mo, to, zero))
 
             def sectors(sec=sec, cloud=cloud, npts=npts, so=so):
@@ -622,7 +727,7 @@ def steer(a):
             fmt(t[row + " T32"]), fmt(t[row + " SMT"]), med[row + " T"] / med[row + " M"], med[row + " T"] / med[row + " S0"],
             med[row + " SMT"] - med[row + " SM"], cpu))
     if a.parent:
-        lines.append("# the steer of libd2pc_sectors_%s.so (`make sectors SNAME=%s SDEFS=...`) on the same input in the same run; the two builds'" % (a.parent, a.parent))
+        lines.append("# the steer of libd2pc_sectors_%s.so (`make sectors SNAME=%s` of other sources) on the same input in the same run; the two builds'" % (a.parent, a.parent))
         lines.append("# outputs (32 candidates) were compared bit for bit before the timing")
         lines.append("%-62s %-30s %-30s %-30s %-30s %8s %8s" % ("cloud, grid", "T", "T " + a.parent, "T32", "T32 " + a.parent, "T ratio", "T32 ratio"))
         for row, *_ in rows:
@@ -640,9 +745,8 @@ def steer(a):
 
 
 def ground(a):
-    """The landing grid beside the sectors call on the same cloud, and the two forms of its reduction when both are built."""
+    """The landing grid beside the sectors call on the same cloud."""
     prop = torch.cuda.get_device_properties(0)
-    have_ab = all(os.path.exists(d2pc.sectors_library_path(v)) for v in ("gwave", "gplain"))
     size = os.path.getsize(d2pc.sectors_library_path())
     lines = ["# tools/sectors_bench.py --ground --rounds %d --iters %d" % (a.rounds, a.iters),
              "# device draw: %s, %d CUs (one device, one process, ONE run; arms interleaved round by round); libd2pc_sectors.so is %d bytes" % (
@@ -654,29 +758,15 @@ def ground(a):
              "# the camera that looks down and its neighbours reach the grid; the other records are gated out after the transform.",
              "# G = d2pc_sectors_ground_process_device alone (three launches); G0 = the same call with a count of 0: the fixed part;",
              "# C = d2pc_membench_copy moving the bytes G reads (16 B per record); S / S0 = the 72 x 1 sectors call on the same cloud / with a count of 0;",
-             "# wave / plain = libd2pc_sectors_gwave.so / _gplain.so (-DD2PC_SECTORS_GROUND_FORCE_ROUNDS=2 / =0), outputs compared bit for bit with G's first" if have_ab
-             else "# (libd2pc_sectors_gwave.so / _gplain.so are not built: no A/B columns)",
              "# us per call: median (min .. max) over the rounds",
-             "%-52s %9s %6s %-30s %-30s %-30s %-30s %-30s %5s %5s %6s" % ("cloud, grid", "records", "blocks", "G", "G0", "C", "S", "S0", "G/C", "G/S", "G0/S0") +
-             (" %-30s %-30s %10s" % ("wave", "plain", "plain/wave") if have_ab else "")]
+             "%-52s %9s %6s %-30s %-30s %-30s %-30s %-30s %5s %5s %6s" % ("cloud, grid", "records", "blocks", "G", "G0", "C", "S", "S0", "G/C", "G/S", "G0/S0")]
     gen = torch.Generator(device="cuda").manual_seed(1)
     s = torch.cuda.current_stream().cuda_stream
-    nadir = np.array([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]])
     for name, n, w, h, mode, rig_case, holes in CASES[:2]:
         with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx, d2pc.Sectors() as sec:
             prod = Producer(ctx, n, w, h, rig_case, holes, gen)
-            level = torch.randint(94, 99, (n, h, w), generator=gen, device="cuda", dtype=torch.int32).to(torch.uint8)
-            level[prod.frames == 0] = 0
-            prod.frames = level
-            prod(s)
-            torch.cuda.synchronize()
-            ctx.check_async_error()
-            npts = int(prod.offsets.cpu().numpy().view(np.uint32)[n]) if rig_case else int(prod.counts.cpu().numpy().view(np.uint32)[0])
-            ordered = prod.pts[:npts].clone()
-            # the grid's corner from camera 0's own records: 4 m to either side of their median, h0 at their median height
-            mid = np.median(ordered[:min(npts, prod.roi_n // 2), :3].cpu().numpy().astype(np.float64) @ nadir.T + [0.0, 0.0, 10.0], axis=0)
-            step = torch.from_numpy(d2pc.sectors_ground_step(nadir, [0.0, 0.0, 10.0], [np.round(mid[0]) - 4.0, np.round(mid[1]) - 4.0, mid[2]], 8, 8)
-                                    .view(np.int32).copy()).to("cuda")
+            npts, ordered, corner = level_ground(ctx, prod, gen, s)
+            step = ground_step(corner)
             shuffled = ordered[torch.randperm(npts, generator=gen, device="cuda")].contiguous()
             count = torch.tensor([npts], dtype=torch.int32, device="cuda")
             zero = torch.zeros(1, dtype=torch.int32, device="cuda")
@@ -685,49 +775,34 @@ def ground(a):
             dst = torch.empty(half, dtype=torch.uint8, device="cuda")
             s_out = dict(range=torch.empty(sec.n_cells, dtype=torch.float32, device="cuda"), count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
                          nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"), distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
-            for grid in (dict(n_a=16, n_b=16, cell_size=0.5), dict(n_a=64, n_b=64, cell_size=0.125)):
-                grid = dict(grid, max_points=prod.cap, max_spread_q2=d2pc.sectors_ground_spread_of_std(0.002, 0.15), max_step_q=100)
-                sessions = [d2pc.SectorsGround(**grid)]
-                if have_ab:
-                    sessions += [d2pc.SectorsGround(variant=v, **grid) for v in ("gwave", "gplain")]
-                nc = sessions[0].n_cells
-
-                def outputs():
-                    return dict(count=torch.empty(nc, dtype=torch.int32, device="cuda"), sum=torch.empty(nc, dtype=torch.int64, device="cuda"),
-                                sum2=torch.empty(nc, dtype=torch.int64, device="cuda"), mean_q=torch.empty(nc, dtype=torch.int32, device="cuda"),
-                                spread_q2=torch.empty(nc, dtype=torch.int32, device="cuda"), flat=torch.empty(nc, dtype=torch.uint8, device="cuda"),
-                                site=torch.empty(nc, dtype=torch.uint8, device="cuda"), candidates=torch.empty(5, dtype=torch.int64, device="cuda"),
-                                summary=torch.empty(4, dtype=torch.int32, device="cuda"))
-
-                outs = [outputs() for _ in sessions]
+            for grid, _ in GROUND_GRIDS:
+                grid = ground_grid(grid, prod)
+                session = d2pc.SectorsGround(**grid)
+                out = ground_outputs(session.n_cells, 5)
                 for label, cloud in (("producer order", ordered), ("shuffled", shuffled)):
                     def call(g, o, c):
                         return lambda: g.process(cloud, npts, step, counts=c, n_candidates=5, stream_ptr=s, **o)
 
-                    arms = [call(sessions[0], outs[0], count), call(sessions[0], outs[0], zero),
+                    arms = [call(session, out, count), call(session, out, zero),
                             lambda: ctx.membench_copy(src.data_ptr(), dst.data_ptr(), half, s),
                             lambda: sec.process(cloud, npts, counts=count, stream_ptr=s, **s_out),
                             lambda: sec.process(cloud, npts, counts=zero, stream_ptr=s, **s_out)]
-                    arms += [call(g, o, count) for g, o in zip(sessions[1:], outs[1:])]
                     for fn in arms[:1] + arms[2:]:
                         fn()
                     torch.cuda.synchronize()
-                    summary = tuple(int(v) for v in outs[0]["summary"].cpu().numpy().view(np.uint32)[:3])
+                    summary = tuple(int(v) for v in out["summary"].cpu().numpy().view(np.uint32)[:3])
                     assert 0 < summary[0] <= npts, "no record reached the grid"
                     assert rig_case or summary[2] >= 5, "the one-camera frame makes fewer sites than candidates"
-                    assert all(torch.equal(outs[0][k], o[k]) for o in outs[1:] for k in o), "the builds disagree"
                     iters = int(min(max(a.iters, 30000.0 / timed(arms[0], 5)), 4000))
                     t = interleaved(arms, a.rounds, iters)
                     ctx.check_async_error()
                     m = [float(np.median(x)) for x in t]
                     lines.append("%-52s %9d %6d %-30s %-30s %-30s %-30s %-30s %5.2f %5.2f %6.2f" % (
-                        "%s, %d x %d, %s" % (name[:14].strip(), grid["n_a"], grid["n_b"], label), npts, min(sessions[0].blocks, (npts + 1023) // 1024),
-                        fmt(t[0]), fmt(t[1]), fmt(t[2]), fmt(t[3]), fmt(t[4]), m[0] / m[2], m[0] / m[3], m[1] / m[4]) +
-                        (" %-30s %-30s %10.2f" % (fmt(t[5]), fmt(t[6]), m[6] / m[5]) if have_ab else ""))
+                        "%s, %d x %d, %s" % (name[:14].strip(), grid["n_a"], grid["n_b"], label), npts, min(session.blocks, (npts + 1023) // 1024),
+                        fmt(t[0]), fmt(t[1]), fmt(t[2]), fmt(t[3]), fmt(t[4]), m[0] / m[2], m[0] / m[3], m[1] / m[4]))
                     lines.append("#   %d of the records took part, %d flat cells, %d sites" % summary)
                     print(lines[-2], flush=True)
-                for g in sessions:
-                    g.close()
+                session.close()
             prod.close()
         del prod, ordered, shuffled, src, dst
         torch.cuda.empty_cache()
@@ -753,22 +828,12 @@ def terrain(a):
                                                                     "Tall/G0", "Tall/G", "Tnone/G0")]
     gen = torch.Generator(device="cuda").manual_seed(1)
     s = torch.cuda.current_stream().cuda_stream
-    nadir = np.array([[1.0, 0, 0], [0, -1.0, 0], [0, 0, -1.0]])
     name, n, w, h, mode, rig_case, holes = CASES[0]
     with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx, d2pc.Sectors() as sec:
         prod = Producer(ctx, n, w, h, rig_case, holes, gen)
-        level = torch.randint(94, 99, (n, h, w), generator=gen, device="cuda", dtype=torch.int32).to(torch.uint8)
-        level[prod.frames == 0] = 0
-        prod.frames = level
-        prod(s)
-        torch.cuda.synchronize()
-        ctx.check_async_error()
-        npts = int(prod.counts.cpu().numpy().view(np.uint32)[0])
-        cloud = prod.pts[:npts].clone()
-        mid = np.median(cloud[:min(npts, prod.roi_n // 2), :3].cpu().numpy().astype(np.float64) @ nadir.T + [0.0, 0.0, 10.0], axis=0)
-        corner = [np.round(mid[0]) - 4.0, np.round(mid[1]) - 4.0, float(np.float32(mid[2]))]   # a multiple of both cell sizes
-        step = torch.from_numpy(d2pc.sectors_ground_step(nadir, [0.0, 0.0, 10.0], corner, 8, 8).view(np.int32).copy()).to("cuda")
-        lone = torch.from_numpy(d2pc.sectors_ground_step(nadir, [0.0, 0.0, 10.0], corner[:2] + [np.nan], 8, 8).view(np.int32).copy()).to("cuda")
+        npts, cloud, corner = level_ground(ctx, prod, gen, s)
+        step = ground_step(corner)
+        lone = torch.from_numpy(d2pc.sectors_ground_step(NADIR, [0.0, 0.0, 10.0], corner[:2] + [np.nan], 8, 8).view(np.int32).copy()).to("cuda")
         count = torch.tensor([npts], dtype=torch.int32, device="cuda")
         zero = torch.zeros(1, dtype=torch.int32, device="cuda")
         # the steer's input: the sectors call and one update of the memory on the same cloud
@@ -776,24 +841,17 @@ def terrain(a):
         st = d2pc.SectorsSteer(sec.cfg, max_reach_sectors=8, max_reach_layers=0)
         so = dict(count=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"), nearest=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"))
         mo = dict(distance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"))
-        to = dict(clearance_cm=torch.empty(sec.n_cells, dtype=torch.int16, device="cuda"), cost=torch.empty(sec.n_cells, dtype=torch.int32, device="cuda"),
-                  candidates=torch.empty(5, dtype=torch.int64, device="cuda"), summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+        to = steer_outputs(sec.n_cells, 5)
         mstep = torch.from_numpy(d2pc.sectors_memory_step(np.eye(3), [0.0, 0.0, 0.0], 50).view(np.int32).copy()).to("cuda")
         goal = torch.from_numpy(d2pc.sectors_steer_step(sec.cfg.n_sectors // 3, 0, 1, 0).view(np.int32).copy()).to("cuda")
         sec.process(cloud, npts, stream_ptr=s, **so)
         mem.update(cloud, npts, so["count"], so["nearest"], mstep, stream_ptr=s, **mo)
         rows, arms, keep = [], [lambda: st.steer(mo["distance_cm"], goal, n_candidates=5, stream_ptr=s, **to)], []
-        for grid, depth in ((dict(n_a=16, n_b=16, cell_size=0.5), 8), (dict(n_a=64, n_b=64, cell_size=0.125), 16)):
-            grid = dict(grid, max_points=prod.cap, max_spread_q2=d2pc.sectors_ground_spread_of_std(0.002, 0.15), max_step_q=100)
-            g = d2pc.SectorsGround(**grid)
-            nc = g.n_cells
+        for grid, depth in GROUND_GRIDS:
+            g = d2pc.SectorsGround(**ground_grid(grid, prod))
 
-            def outputs():
-                return dict(count=torch.empty(nc, dtype=torch.int32, device="cuda"), sum=torch.empty(nc, dtype=torch.int64, device="cuda"),
-                            sum2=torch.empty(nc, dtype=torch.int64, device="cuda"), mean_q=torch.empty(nc, dtype=torch.int32, device="cuda"),
-                            spread_q2=torch.empty(nc, dtype=torch.int32, device="cuda"), flat=torch.empty(nc, dtype=torch.uint8, device="cuda"),
-                            site=torch.empty(nc, dtype=torch.uint8, device="cuda"), candidates=torch.empty(5, dtype=torch.int64, device="cuda"),
-                            summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+            def outputs(nc=g.n_cells):
+                return ground_outputs(nc, 5)
 
             go, g0, t_all, t_none = outputs(), outputs(), outputs(), outputs()
             status = [torch.zeros(4, dtype=torch.int32, device="cuda") for _ in range(2)]
@@ -846,7 +904,7 @@ def main():
     ap.add_argument("--ground", action="store_true", help="the landing grid beside the sectors call instead of the cost table")
     ap.add_argument("--terrain", action="store_true", help="the terrain's update beside the ground call and the steer call instead of the cost table")
     ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
-                    "alone, the table of this build against it (S of four grids, M of two)")
+                    "alone, the table of this build against it (S, M, T, T32, G and the terrain's update)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.parent and (a.memory or a.ab or a.ground or a.terrain):

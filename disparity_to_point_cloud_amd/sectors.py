@@ -34,6 +34,9 @@ SECTORS_SYMBOLS = [
     "d2pc_sectors_terrain_config_init", "d2pc_sectors_terrain_geometry", "d2pc_sectors_terrain_create", "d2pc_sectors_terrain_destroy",
     "d2pc_sectors_terrain_last_error", "d2pc_sectors_terrain_state", "d2pc_sectors_terrain_reset_device", "d2pc_sectors_terrain_desc_init",
     "d2pc_sectors_terrain_desc_check", "d2pc_sectors_terrain_update_device",
+    "d2pc_sectors_slope_config_init", "d2pc_sectors_slope_geometry", "d2pc_sectors_slope_of_degrees", "d2pc_sectors_slope_create",
+    "d2pc_sectors_slope_destroy", "d2pc_sectors_slope_last_error", "d2pc_sectors_slope_blocks", "d2pc_sectors_slope_desc_init",
+    "d2pc_sectors_slope_desc_check", "d2pc_sectors_slope_process_device",
 ]
 EMPTY_AGE, OLDEST_AGE = 0xFFFFFFFF, 0xFFFFFFFE   # the age word of an empty record; where an age saturates
 STEER_MAX_REACH_SECTORS, STEER_MAX_REACH_LAYERS, STEER_MAX_CANDIDATES, STEER_MAX_WEIGHT = 32, 16, 32, 4095
@@ -45,6 +48,8 @@ GROUND_EMPTY_MEAN, GROUND_EMPTY_SPREAD = 0x80000000, 0xFFFFFFFF   # mean_q (as a
 GROUND_OFF = 0xFFFFFFFF           # a goal_i / goal_j that switches the distance term off
 GROUND_NO_CANDIDATE = 0xFFFFFFFFFFFFFFFF  # a candidate slot beyond the sites
 TERRAIN_MAX_DEPTH, TERRAIN_HEADER_BYTES, TERRAIN_MAX_CORNER = 16, 16, 536870912
+SLOPE_CELL_BYTES, SLOPE_MAX_CELLS, SLOPE_MOMENTS = 76, 2155, 7
+SLOPE_NOT_FITTED = 0x7FC00000     # slope_a / slope_b of a cell that is not fitted, as bits
 
 
 class SectorsConfig(ctypes.Structure):
@@ -177,6 +182,29 @@ class SectorsTerrainDesc(ctypes.Structure):
     ]
 
 
+class SectorsSlopeConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("sub", ctypes.c_int32), ("max_slope", ctypes.c_float), ("reserved", ctypes.c_uint32 * 5)]
+
+
+class SectorsSlopeGeometry(ctypes.Structure):
+    _fields_ = [
+        ("n_cells", ctypes.c_int32), ("blocks_per_cu", ctypes.c_int32), ("blocks", ctypes.c_int32), ("sub", ctypes.c_int32),
+        ("lds_bytes", ctypes.c_size_t), ("block_bytes", ctypes.c_size_t), ("device_bytes", ctypes.c_size_t),
+        ("scale", ctypes.c_double), ("max_tilt2", ctypes.c_double), ("reserved", ctypes.c_int32 * 4),
+    ]
+
+
+class SectorsSlopeDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("point_step", ctypes.c_int32), ("n_clouds", ctypes.c_int32), ("n_candidates", ctypes.c_int32),
+        ("points", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("cloud_points", ctypes.c_size_t),
+        ("points_frame_stride_points", ctypes.c_size_t), ("step", ctypes.c_void_p), ("allowed", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("sum", ctypes.c_void_p), ("sum2", ctypes.c_void_p), ("moments", ctypes.c_void_p),
+        ("slope_a", ctypes.c_void_p), ("slope_b", ctypes.c_void_p), ("level_q", ctypes.c_void_p), ("resid_q2", ctypes.c_void_p),
+        ("flat", ctypes.c_void_p), ("site", ctypes.c_void_p), ("candidates", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -276,6 +304,22 @@ def load_sectors_library(variant=None):
         L.d2pc_sectors_terrain_desc_init.restype = None
         L.d2pc_sectors_terrain_desc_check.argtypes = [gcfg, tcfg, tdesc]
         L.d2pc_sectors_terrain_update_device.argtypes = [vp, tdesc, vp]
+    if variant is None or hasattr(L, "d2pc_sectors_slope_create"):   # (an A/B variant may be a build from before the slope)
+        gcfg, scfg, sdesc = ctypes.POINTER(SectorsGroundConfig), ctypes.POINTER(SectorsSlopeConfig), ctypes.POINTER(SectorsSlopeDesc)
+        L.d2pc_sectors_slope_config_init.argtypes = [scfg]
+        L.d2pc_sectors_slope_config_init.restype = None
+        L.d2pc_sectors_slope_geometry.argtypes = [gcfg, scfg, ctypes.POINTER(SectorsSlopeGeometry)]
+        L.d2pc_sectors_slope_of_degrees.argtypes = [ctypes.c_double]
+        L.d2pc_sectors_slope_of_degrees.restype = ctypes.c_float
+        L.d2pc_sectors_slope_create.argtypes = [gcfg, scfg, ctypes.POINTER(vp)]
+        L.d2pc_sectors_slope_destroy.argtypes = [vp]
+        L.d2pc_sectors_slope_last_error.argtypes = [vp]
+        L.d2pc_sectors_slope_last_error.restype = ctypes.c_char_p
+        L.d2pc_sectors_slope_blocks.argtypes = [vp]
+        L.d2pc_sectors_slope_desc_init.argtypes = [sdesc]
+        L.d2pc_sectors_slope_desc_init.restype = None
+        L.d2pc_sectors_slope_desc_check.argtypes = [gcfg, scfg, sdesc]
+        L.d2pc_sectors_slope_process_device.argtypes = [vp, sdesc, vp]
     if variant is None:
         _lib = L
     return L
@@ -716,3 +760,69 @@ class SectorsTerrain(_Session):
         st = self._L.d2pc_sectors_terrain_reset_device(self._h, stream_ptr)
         if st:
             raise D2pcError(st, self.last_error())
+
+
+def sectors_slope_config_init(**kw) -> SectorsSlopeConfig:
+    """d2pc_sectors_slope_config_init, then the given fields."""
+    c = SectorsSlopeConfig()
+    load_sectors_library().d2pc_sectors_slope_config_init(ctypes.byref(c))
+    return _set(c, kw)
+
+
+def sectors_slope_desc_init(**kw) -> SectorsSlopeDesc:
+    """d2pc_sectors_slope_desc_init, then the given fields."""
+    d = SectorsSlopeDesc()
+    load_sectors_library().d2pc_sectors_slope_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_slope_geometry(gcfg: SectorsGroundConfig, scfg: SectorsSlopeConfig) -> SectorsSlopeGeometry:
+    """d2pc_sectors_slope_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = SectorsSlopeGeometry()
+    st = load_sectors_library().d2pc_sectors_slope_geometry(ctypes.byref(gcfg), ctypes.byref(scfg), ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "sectors_slope_geometry(%d x %d, sub %d)" % (gcfg.n_a, gcfg.n_b, scfg.sub))
+    return g
+
+
+def sectors_slope_of_degrees(degrees) -> float:
+    """d2pc_sectors_slope_of_degrees: max_slope (rise over run, a float32) from an angle."""
+    return float(load_sectors_library().d2pc_sectors_slope_of_degrees(degrees))
+
+
+def sectors_slope_desc_check(gcfg: SectorsGroundConfig, scfg: SectorsSlopeConfig, desc: SectorsSlopeDesc) -> int:
+    """d2pc_sectors_slope_desc_check: the status d2pc_sectors_slope_process_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_slope_desc_check(ctypes.byref(gcfg), ctypes.byref(scfg), ctypes.byref(desc))
+
+
+class SectorsSlope(_Session):
+    """d2pc_sectors_slope_*: a plane fit per cell of the landing grid -- slope along a and b, the level at the cell's centre,
+    the roughness about the plane -- and ranked landing sites, from any cloud and a pose (a sectors_ground_step).  `process`
+    takes torch tensors or raw device pointers, is asynchronous on `stream` and allocates nothing."""
+
+    _PREFIX = "d2pc_sectors_slope"
+
+    def __init__(self, gcfg: SectorsGroundConfig, scfg: SectorsSlopeConfig = None, variant=None, **kw):
+        self.cfg = gcfg
+        self.scfg = _set(scfg, kw) if scfg is not None else sectors_slope_config_init(**kw)
+        self._create(variant, "sectors_slope_create(%d x %d, sub %d)" % (gcfg.n_a, gcfg.n_b, self.scfg.sub),
+                     ctypes.byref(self.cfg), ctypes.byref(self.scfg))
+        self.geometry = sectors_slope_geometry(self.cfg, self.scfg)
+        self.n_cells, self.blocks = self.geometry.n_cells, int(self._L.d2pc_sectors_slope_blocks(self._h))
+
+    def process_desc(self, desc: SectorsSlopeDesc, stream_ptr=None):
+        """d2pc_sectors_slope_process_device."""
+        st = self._L.d2pc_sectors_slope_process_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def process(self, points, cloud_points, step, point_step=16, n_clouds=1, counts=None, frame_stride_points=0, allowed=None,
+                count=None, sum=None, sum2=None, moments=None, slope_a=None, slope_b=None, level_q=None, resid_q2=None, flat=None,
+                site=None, candidates=None, n_candidates=1, summary=None, stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.process_desc(sectors_slope_desc_init(
+            point_step=point_step, n_clouds=n_clouds, n_candidates=n_candidates, points=_ptr(points), counts=_ptr(counts),
+            cloud_points=cloud_points, points_frame_stride_points=frame_stride_points, step=_ptr(step), allowed=_ptr(allowed),
+            count=_ptr(count), sum=_ptr(sum), sum2=_ptr(sum2), moments=_ptr(moments), slope_a=_ptr(slope_a), slope_b=_ptr(slope_b),
+            level_q=_ptr(level_q), resid_q2=_ptr(resid_q2), flat=_ptr(flat), site=_ptr(site), candidates=_ptr(candidates),
+            summary=_ptr(summary)), stream_ptr)

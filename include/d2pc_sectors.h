@@ -266,6 +266,61 @@
  *     6. status = {q, the slots that took part (the frame included), (uint32)ia0, (uint32)jb0}.
  *     7. The guarantee holds for tables that ground calls wrote.  For other tables the per-cell outputs follow the wrapping
  *        formulas, and site / candidates are unspecified.
+ *
+ * --------------------------------------------------------------------------------------- SLOPE (d2pc_sectors_slope_*)
+ * The ground judges a cell by spread_q2 alone, and a smooth 15 degree slope spreads a 0.5 m cell by 3.9 cm: as much as a
+ * level cell full of rubble.  The slope session fits ONE plane per cell, k ~ c0 + gu u + gw w, so a planner reads how steep
+ * a cell is (slope_a, slope_b: which way it falls), and how rough it is about its own plane (resid_q2).  It takes the
+ * ground's configuration unchanged and a d2pc_sectors_slope_config beside it; d2pc_sectors_slope_process_device makes the
+ * grid in at most three launches.  Every accumulated value is an integer, and the fit is one fixed sequence of double
+ * operations per cell, each rounded once: the result is the same bytes whatever order the device visits the points in.
+ * tests/sectors_slope_ref.py restates it in numpy.
+ *
+ * Configuration (d2pc_sectors_slope_config):  sub = P, the in-cell position steps per axis, 2, 4, 8 or 16;  max_slope, a
+ * float, rise over run, finite and >= 0.  The host forms, in double,
+ *     max_tilt2 = (double)max_slope * (double)max_slope        scale = (double)quantum * (2 * P) / (double)cell_size
+ * (scale = fl(fl((double)quantum * (double)(2 * P)) / (double)cell_size): a slope in quanta per half sub-step times scale is
+ * rise over run).
+ *
+ * Per record.  Steps 1 .. 8 of the GROUND block, word for word: the same step of 80 bytes, the same gate, cell and k.  Then
+ *     9. fa = fl(va - floorf(va)),  pa = (int)floorf(fl(fa * P)),  u = 2 pa - (P - 1);  w likewise from vb.  Both float
+ *        operations are exact (va < 64 and P is a power of two), so u and w are odd integers in [-(P - 1), P - 1]: the
+ *        position in the cell in half sub-steps from its centre.
+ *
+ * Cell.  The ground's count, sum and sum2, and seven more sums over the same points, all int64:
+ *     su = sum u   sw = sum w   suu = sum u^2   suw = sum u w   sww = sum w^2   suk = sum u k   swk = sum w k
+ * Every term is below 2^19 in magnitude: exact for any call of fewer than 2^32 positions, the same bytes in any order.
+ *
+ * Fit, once per cell with count > 0.  First in wrapping 64-bit integers: m and S are the ground's floor mean and its S;
+ *     r = sum - count m        suk' = suk - m su        swk' = swk - m sw
+ * Then count (N), su, sw, suu, suw, sww, suk', swk', r (as int64) and S (as uint64) are converted to double, round to
+ * nearest even (exact below 2^53: cells of fewer than 2^23 points).  Then, every operation in double and rounded once,
+ * nothing contracted, each product of a difference rounded before the subtraction:
+ *     A = N suu - su su     B = N suw - su sw     C = N sww - sw sw
+ *     E = N suk' - su r     F = N swk' - sw r     G = N S - r r
+ *     D = A C - B B
+ *     fitted  =  count >= max(min_count, 3)  and  A C > 0  and  D * 1048576.0 > A C
+ *     gu = (E C - F B) / D          gw = (F A - E B) / D
+ *     Q  = (G - gu E) - gw F        c0 = ((r - gu su) - gw sw) / N
+ * The third test of `fitted` refuses collinear and near-collinear point sets: it asks 1 - rho^2 > 2^-20, far above what
+ * rounding can fake.
+ *
+ * Outputs, n_cells entries each, each nullable, at least one given:
+ *     count, sum, sum2   the ground's bytes: a terrain session can still be fed
+ *     moments    int64 x 7 x n_cells, 8-byte aligned: su, sw, suu, suw, sww, suk, swk, plane after plane (moments[p * n_cells
+ *                + cell]).  A caller adds them across frames
+ *     slope_a    float32  (float)(gu * scale): the rise along a per unit of run;  slope_b likewise from gw.  A cell that is
+ *                not fitted gets the quiet NaN of bits 0x7FC00000
+ *     level_q    int32    fitted: m + (int)rint(c0), half to even -- the plane at the cell's centre (rint(c0) is clamped to
+ *                [-2^31, 2^31 - 1] before the conversion and the sum wraps in 32 bits; no flat cell comes near).  A cell
+ *                that has points but is not fitted: m.  An empty cell: 0x80000000
+ *     resid_q2   uint32   fitted: floor(max(Q, 0) / (N N)), 0xFFFFFFFE from 4294967294.0 on -- the mean squared residual
+ *                about the plane (N N is one rounded product).  Points but not fitted: the ground's spread_q2.  Empty:
+ *                0xFFFFFFFF
+ *     flat       uint8    1 when the cell is fitted, resid_q2 <= max_spread_q2 and sa sa + sb sb <= max_tilt2 in double,
+ *                sa = gu * scale, sb = gw * scale
+ *     site, candidates, summary   the GROUND block's, word for word, with level_q for mean_q, resid_q2 for spread_q2 and
+ *                this flat for the ground's; summary word 3 is the number of fitted cells
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -724,6 +779,94 @@ int d2pc_sectors_terrain_desc_check(const d2pc_sectors_ground_config *gcfg, cons
  * session: one update of a session in flight per stream order.
  */
 int d2pc_sectors_terrain_update_device(d2pc_sectors_terrain *t, const d2pc_sectors_terrain_desc *desc, void *stream);
+
+/* -------------------------------------------------------------------------------------------------------- the slope */
+#define D2PC_SECTORS_SLOPE_CELL_BYTES 76            /* of a reducing block's table and of its slab: nine 64-bit sums and the count */
+#define D2PC_SECTORS_SLOPE_MAX_CELLS 2155           /* 76 bytes per cell in the 163,840 bytes of one block's LDS */
+#define D2PC_SECTORS_SLOPE_MOMENTS 7                /* planes of `moments`: su, sw, suu, suw, sww, suk, swk */
+#define D2PC_SECTORS_SLOPE_NOT_FITTED 0x7FC00000u   /* slope_a / slope_b of a cell that is not fitted, as bits */
+
+typedef struct d2pc_sectors_slope_config {   /* fixed for a slope session, beside the ground configuration */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_slope_config) */
+  int32_t sub;                 /* P: 2, 4, 8 or 16 in-cell position steps per axis */
+  float max_slope;             /* finite and >= 0, rise over run: a steeper cell is not flat (d2pc_sectors_slope_of_degrees makes it) */
+  uint32_t reserved[5];        /* zero */
+} d2pc_sectors_slope_config;
+/* sub 8, max_slope 0.26794919 (15 degrees). */
+void d2pc_sectors_slope_config_init(d2pc_sectors_slope_config *scfg);
+
+typedef struct d2pc_sectors_slope_geometry_t {
+  int32_t n_cells;             /* n_a * n_b: entries of every per-cell output */
+  int32_t blocks_per_cu;       /* reducing blocks per compute unit: as many as 160 KiB of LDS hold, 4 at the most */
+  int32_t blocks;              /* reducing blocks of a session on an MI355X: the ground's arithmetic with this blocks_per_cu */
+  int32_t sub;                 /* P */
+  size_t lds_bytes;            /* of one reducing block: 76 bytes per cell */
+  size_t block_bytes;          /* device memory the session holds PER BLOCK: 76 bytes per cell, rounded up to a multiple of 8 */
+  size_t device_bytes;         /* what a session holds on an MI355X: the slabs and 14 bytes per cell between the launches */
+  double scale, max_tilt2;     /* as the specification forms them */
+  int32_t reserved[4];
+} d2pc_sectors_slope_geometry_t;
+/* Host arithmetic only, no device.  A NULL `out` is D2PC_ERR_INVALID_ARG before everything.  First the refusals of
+ * d2pc_sectors_ground_geometry for `gcfg`, unchanged; then, in this order, D2PC_ERR_INVALID_ARG: a NULL scfg or its
+ * struct_size, a sub that is not 2, 4, 8 or 16, a max_slope that is NaN, not finite or negative, a reserved word that is
+ * not zero;  D2PC_ERR_BAD_SIZE: n_cells * 76 > 163,840 (more than 2,155 cells: 46 x 46 and 64 x 32 pass, 64 x 64 does not). */
+int d2pc_sectors_slope_geometry(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_slope_config *scfg,
+                                d2pc_sectors_slope_geometry_t *out);
+/* Host only, in double: max_slope from an angle, (float)tan(degrees * pi / 180).  0 for an angle that is NaN, negative or
+ * 90 and more. */
+float d2pc_sectors_slope_of_degrees(double degrees);
+
+typedef struct d2pc_sectors_slope d2pc_sectors_slope;
+/* Allocates everything the session will ever need (the blocks' slabs and 14 bytes per cell that the launches hand on).
+ * D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
+int d2pc_sectors_slope_create(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_slope_config *scfg, d2pc_sectors_slope **out);
+int d2pc_sectors_slope_destroy(d2pc_sectors_slope *s);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_slope_last_error(const d2pc_sectors_slope *s);
+/* Reducing blocks this session holds slabs for (0 for NULL).  A call launches min(blocks, its shares) of them. */
+int d2pc_sectors_slope_blocks(const d2pc_sectors_slope *s);
+
+typedef struct d2pc_sectors_slope_desc {   /* d2pc_sectors_ground_desc with the slope's outputs */
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_slope_desc) */
+  int32_t point_step;          /* 16 or 32 */
+  int32_t n_clouds;            /* 1 .. 65,535 */
+  int32_t n_candidates;        /* 1 .. 32 when `candidates` is given */
+  const void *points;          /* DEVICE: the records, 16-byte aligned */
+  const uint32_t *counts;      /* DEVICE, nullable: as d2pc_sectors_desc */
+  size_t cloud_points;         /* 1 .. 2^32 - 1 */
+  size_t points_frame_stride_points;
+  const d2pc_sectors_ground_step *step;   /* DEVICE, 4-byte aligned */
+  const uint8_t *allowed;      /* DEVICE, nullable: one byte per cell, zero = no site */
+  uint32_t *count;             /* DEVICE out, each nullable; at least one of the twelve is given */
+  int64_t *sum;                /* 8-byte aligned */
+  uint64_t *sum2;              /* 8-byte aligned */
+  int64_t *moments;            /* 7 x n_cells, 8-byte aligned */
+  float *slope_a, *slope_b;
+  int32_t *level_q;
+  uint32_t *resid_q2;
+  uint8_t *flat;
+  uint8_t *site;
+  d2pc_sectors_ground_candidate *candidates;   /* n_candidates records, 8-byte aligned */
+  uint32_t *summary;           /* 4 words */
+} d2pc_sectors_slope_desc;
+/* struct_size, point_step 16, n_clouds 1, n_candidates 1; everything else zero. */
+void d2pc_sectors_slope_desc_init(d2pc_sectors_slope_desc *desc);
+/* Host only: what d2pc_sectors_slope_process_device refuses of `desc`, without a session; first the refusals of the two
+ * configurations as d2pc_sectors_slope_geometry makes them.  Then the ground descriptor's, in its order, with the new
+ * outputs beside the old: D2PC_ERR_INVALID_ARG: NULL, struct_size, point_step, n_clouds, a NULL points or step, no output,
+ * n_candidates out of 1 .. 32 when candidates is given, points not 16-byte aligned, another pointer not aligned to its type
+ * (8 bytes for sum, sum2, moments and candidates), an output that overlaps points, counts, step, allowed or another output.
+ * D2PC_ERR_BAD_SIZE: cloud_points, the frame stride and the largest position as d2pc_sectors_desc_check refuses them. */
+int d2pc_sectors_slope_desc_check(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_slope_config *scfg,
+                                  const d2pc_sectors_slope_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): three launches (two when neither site, candidates nor summary
+ * is asked for), no memset, no allocation, no count read on the host -- it can be captured into a graph as it is, behind
+ * its producer, and replays with a new pose after one 80-byte copy into `step`.  Every refusal is made before anything is
+ * enqueued.  Bit-reproducible: every sum is of integers and the fit is one fixed sequence of double operations per cell.
+ * The slabs belong to the session: one call of a session in flight per stream order; two streams need two sessions.
+ */
+int d2pc_sectors_slope_process_device(d2pc_sectors_slope *s, const d2pc_sectors_slope_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

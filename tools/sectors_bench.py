@@ -60,6 +60,14 @@ ranks them).  GPU box only.
                                             64 x 64 at depth 16, with every slot of the window taking part and with none, beside the ground
                                             call's G and G0 and the steer call on the same one-camera cloud, in ONE interleaved run.  No
                                             time is fixed in advance: T is read against G0 and G of its row
+  python tools/sectors_bench.py --slope
+                                        ->  profiles/sectors_slope_bench.txt: the plane fit per cell (d2pc_sectors_slope_process_device,
+                                            three launches, ten LDS adds a record and slabs of 76 bytes a cell) beside the ground call of
+                                            the same configuration (three adds, 20 bytes): L = the slope call, L0 = with a count of 0, G and
+                                            G0 = the ground's, C = the copy of the bytes they read, for 16 x 16 and 46 x 46 cells, the
+                                            one-camera frame and the rig's merged cloud, in producer order and shuffled, in ONE interleaved
+                                            run.  No time is fixed in advance: L is read against G and C of its row; L0 - G0 is what the
+                                            larger slabs cost, (L - L0) - (G - G0) what the seven more adds a record cost
 """
 import argparse
 import os
@@ -809,6 +817,85 @@ def ground(a):
     return lines
 
 
+SLOPE_GRIDS = [dict(n_a=16, n_b=16, cell_size=0.5), dict(n_a=46, n_b=46, cell_size=0.125)]
+
+
+def slope_outputs(nc, k):
+    return dict(count=torch.empty(nc, dtype=torch.int32, device="cuda"), sum=torch.empty(nc, dtype=torch.int64, device="cuda"),
+                sum2=torch.empty(nc, dtype=torch.int64, device="cuda"), moments=torch.empty(7 * nc, dtype=torch.int64, device="cuda"),
+                slope_a=torch.empty(nc, dtype=torch.float32, device="cuda"), slope_b=torch.empty(nc, dtype=torch.float32, device="cuda"),
+                level_q=torch.empty(nc, dtype=torch.int32, device="cuda"), resid_q2=torch.empty(nc, dtype=torch.int32, device="cuda"),
+                flat=torch.empty(nc, dtype=torch.uint8, device="cuda"), site=torch.empty(nc, dtype=torch.uint8, device="cuda"),
+                candidates=torch.empty(k, dtype=torch.int64, device="cuda"), summary=torch.empty(4, dtype=torch.int32, device="cuda"))
+
+
+def slope(a):
+    """The plane fit per cell beside the ground call of the same configuration on the same cloud."""
+    prop = torch.cuda.get_device_properties(0)
+    size = os.path.getsize(d2pc.sectors_library_path())
+    lines = ["# tools/sectors_bench.py --slope --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; arms interleaved round by round); libd2pc_sectors.so is %d bytes" % (
+                 prop.name, prop.multi_processor_count, size),
+             "# the cloud is tools/sectors_bench.py --ground's: a level ground 5.4 m below a camera that looks straight down (30 % holes), the nadir pose in",
+             "# the step.  The grid lies under the camera: 16 x 16 cells of 0.5 m or 46 x 46 of 0.125 m (the largest square table of one block's LDS: 160,816",
+             "# bytes, one block a CU), quantum 0.002, sub 8, max_slope tan 15 deg, max_points = the cloud's capacity, every output with 5 candidates.",
+             "# L = d2pc_sectors_slope_process_device alone (three launches, all twelve outputs); L0 = the same call with a count of 0: the fixed part (tables",
+             "# initialised, slabs of 76 bytes a cell stored and merged, the fit, the sites); G / G0 = d2pc_sectors_ground_process_device of the same",
+             "# configuration, likewise (nine outputs, slabs of 20 bytes a cell); C = d2pc_membench_copy moving the bytes L and G read (16 B per record).",
+             "# slabs = L0 - G0: what the larger tables cost with no record read; adds = (L - L0) - (G - G0): what ten LDS adds a record cost over three.",
+             "# us per call: median (min .. max) over the rounds.  No time was fixed in advance",
+             "%-52s %9s %7s %-30s %-30s %-30s %-30s %-30s %5s %5s %6s %7s %7s" % ("cloud, grid", "records", "blocks", "L", "L0", "G", "G0", "C", "L/G", "L/C", "L0/G0",
+                                                                            "slabs", "adds")]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    for name, n, w, h, mode, rig_case, holes in CASES[:2]:
+        with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx:
+            prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+            npts, ordered, corner = level_ground(ctx, prod, gen, s)
+            step = ground_step(corner)
+            shuffled = ordered[torch.randperm(npts, generator=gen, device="cuda")].contiguous()
+            count = torch.tensor([npts], dtype=torch.int32, device="cuda")
+            zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+            half = max(16 * npts // 2 // 16 * 16, 16)
+            src = torch.empty(half, dtype=torch.uint8, device="cuda")
+            dst = torch.empty(half, dtype=torch.uint8, device="cuda")
+            for grid in SLOPE_GRIDS:
+                grid = ground_grid(grid, prod)
+                gnd = d2pc.SectorsGround(**grid)
+                slp = d2pc.SectorsSlope(gnd.cfg)
+                g_out, l_out = ground_outputs(gnd.n_cells, 5), slope_outputs(slp.n_cells, 5)
+                for label, cloud in (("producer order", ordered), ("shuffled", shuffled)):
+                    def call(x, o, c):
+                        return lambda: x.process(cloud, npts, step, counts=c, n_candidates=5, stream_ptr=s, **o)
+
+                    arms = [call(slp, l_out, count), call(slp, l_out, zero), call(gnd, g_out, count), call(gnd, g_out, zero),
+                            lambda: ctx.membench_copy(src.data_ptr(), dst.data_ptr(), half, s)]
+                    for fn in (arms[0], arms[2], arms[4]):
+                        fn()
+                    torch.cuda.synchronize()
+                    ls = tuple(int(v) for v in l_out["summary"].cpu().numpy().view(np.uint32))
+                    gs = tuple(int(v) for v in g_out["summary"].cpu().numpy().view(np.uint32))
+                    assert 0 < ls[0] <= npts and ls[0] == gs[0], "the two calls took different records"
+                    assert torch.equal(l_out["count"], g_out["count"]) and torch.equal(l_out["sum2"], g_out["sum2"])
+                    iters = int(min(max(a.iters, 30000.0 / timed(arms[0], 5)), 4000))
+                    t = interleaved(arms, a.rounds, iters)
+                    ctx.check_async_error()
+                    m = [float(np.median(x)) for x in t]
+                    lines.append("%-52s %9d %7s %-30s %-30s %-30s %-30s %-30s %5.2f %5.2f %6.2f %7.1f %7.1f" % (
+                        "%s, %d x %d, %s" % (name[:14].strip(), grid["n_a"], grid["n_b"], label), npts,
+                        "%d/%d" % (min(slp.blocks, (npts + 1023) // 1024), min(gnd.blocks, (npts + 1023) // 1024)),
+                        fmt(t[0]), fmt(t[1]), fmt(t[2]), fmt(t[3]), fmt(t[4]), m[0] / m[2], m[0] / m[4], m[1] / m[3], m[1] - m[3], (m[0] - m[1]) - (m[2] - m[3])))
+                    lines.append("#   %d of the records took part; slope: %d flat cells, %d sites, %d fitted; ground: %d flat cells, %d sites" % (
+                        ls[0], ls[1], ls[2], ls[3], gs[1], gs[2]))
+                    print(lines[-2], flush=True)
+                slp.close()
+                gnd.close()
+            prod.close()
+        del prod, ordered, shuffled, src, dst
+        torch.cuda.empty_cache()
+    return lines
+
+
 def terrain(a):
     """The terrain's update alone beside the ground call that feeds it and the steer call, on one cloud, in one run."""
     prop = torch.cuda.get_device_properties(0)
@@ -903,16 +990,17 @@ def main():
     ap.add_argument("--steer", action="store_true", help="the steer call beside the sectors call and the memory's update instead of the cost table")
     ap.add_argument("--ground", action="store_true", help="the landing grid beside the sectors call instead of the cost table")
     ap.add_argument("--terrain", action="store_true", help="the terrain's update beside the ground call and the steer call instead of the cost table")
+    ap.add_argument("--slope", action="store_true", help="the plane fit per cell beside the ground call instead of the cost table")
     ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
                     "alone, the table of this build against it (S, M, T, T32, G and the terrain's update)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.parent and (a.memory or a.ab or a.ground or a.terrain):
+    if a.parent and (a.memory or a.ab or a.ground or a.terrain or a.slope):
         ap.error("--parent goes with --elevation or --steer or stands alone (its own table holds the memory's rows)")
     versus = bool(a.parent) and not (a.memory or a.elevation or a.ab or a.steer)
-    if a.ground or a.terrain:
-        lines = terrain(a) if a.terrain else ground(a)
-        out = a.out or os.path.join(ROOT, "profiles", "sectors_terrain_bench.txt" if a.terrain else "sectors_ground_bench.txt")
+    if a.ground or a.terrain or a.slope:
+        lines = slope(a) if a.slope else terrain(a) if a.terrain else ground(a)
+        out = a.out or os.path.join(ROOT, "profiles", "sectors_slope_bench.txt" if a.slope else "sectors_terrain_bench.txt" if a.terrain else "sectors_ground_bench.txt")
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
         print("wrote", out)

@@ -13,13 +13,13 @@
 //                    per-cell outputs the caller asked for and the 14 bytes per cell the sites read.
 // k_slope_sites      ONE block of 1,024 lanes that calls ground_site_stage (d2pc_sectors_ground_sites.hpp) on level_q,
 //                    resid_q2 and the slope's flat, and then stores the number of fitted cells over summary word 3.
+// The fit and the site launch's body are d2pc_sectors_slope_fit.hpp's: the relief's kernels call the same.
 // Every accumulated value is an integer and the fit is one fixed sequence of double operations per cell: the result is the
 // same bytes whatever order lanes, waves and blocks arrive in.  Every float and double expression of the specification is
 // rounded once: contraction is off in this file.
 #include <hip/hip_runtime.h>
 
-#include "d2pc_sectors_ground_sites.hpp"
-#include "d2pc_sectors_slope_plan.hpp"
+#include "d2pc_sectors_slope_fit.hpp"
 
 namespace d2pc {
 namespace sectors {
@@ -43,8 +43,7 @@ struct SlopeArgs {   // SlopeLaunch without its host-only members
   uint32_t flip_a, flip_b, flip_h;
   float inv_c, inv_q, sub;
   int sub_less_1;
-  uint32_t min_fit, max_spread_q2;   // min_fit = max(min_count, 3)
-  double scale, max_tilt2;
+  SlopeFit fit;   // (d2pc_sectors_slope_fit.hpp)
 };
 
 // the block's slab: the nine 64-bit planes of n_cells each, then the counts
@@ -132,47 +131,6 @@ __global__ __launch_bounds__(kThreads) void k_slope_reduce(const SlopeArgs a) {
   for (int i = int(tid); i < n_cells; i += kThreads) slab_c[i] = cnt[i];
 }
 
-// what the fit makes of a cell
-struct SlopeCell {
-  uint32_t slope_a, slope_b, level_q, resid_q2;   // the floats as bits
-  uint8_t flat, fitted;
-};
-
-// The SLOPE block's fit of one cell from its count and nine sums s[] (sum, sum2, su, sw, suu, suw, sww, suk, swk).
-__device__ __forceinline__ SlopeCell slope_cell_fit(const SlopeArgs &a, uint32_t cnt, const unsigned long long (&s)[kSlopeWords]) {
-#pragma clang fp contract(off)
-  SlopeCell o;
-  uint32_t mean, spread;
-  ground_cell_formula(cnt, s[0], s[1], &mean, &spread);   // (d2pc_sectors_ground_sites.hpp: m and floor(S / count), the empty cell's words)
-  o.slope_a = o.slope_b = D2PC_SECTORS_SLOPE_NOT_FITTED, o.level_q = mean, o.resid_q2 = spread, o.flat = 0, o.fitted = 0;
-  if (cnt == 0u) return o;
-  // the integer pre-steps, wrapping
-  const unsigned long long um = static_cast<unsigned long long>(static_cast<long long>(int(mean))), uc = cnt;
-  const unsigned long long uS = s[1] - 2ull * um * s[0] + uc * um * um;
-  const double N = double(cnt), S = double(uS);
-  const double r = double(static_cast<long long>(s[0] - uc * um));
-  const double su = double(static_cast<long long>(s[2])), sw = double(static_cast<long long>(s[3]));
-  const double suu = double(static_cast<long long>(s[4])), suw = double(static_cast<long long>(s[5])), sww = double(static_cast<long long>(s[6]));
-  const double suk = double(static_cast<long long>(s[7] - um * s[2])), swk = double(static_cast<long long>(s[8] - um * s[3]));
-  const double A = N * suu - su * su, B = N * suw - su * sw, C = N * sww - sw * sw;
-  const double E = N * suk - su * r, F = N * swk - sw * r, G = N * S - r * r;
-  const double AC = A * C;
-  const double D = AC - B * B;
-  if (!(cnt >= a.min_fit && AC > 0.0 && D * 1048576.0 > AC)) return o;
-  const double gu = (E * C - F * B) / D, gw = (F * A - E * B) / D;
-  const double Q = (G - gu * E) - gw * F, c0 = ((r - gu * su) - gw * sw) / N;
-  const double sa = gu * a.scale, sb = gw * a.scale;
-  double rc = rint(c0);
-  rc = rc < -2147483648.0 ? -2147483648.0 : (rc > 2147483647.0 ? 2147483647.0 : rc);
-  const double mq = floor((Q > 0.0 ? Q : 0.0) / (N * N));
-  o.fitted = 1;
-  o.slope_a = __float_as_uint(float(sa)), o.slope_b = __float_as_uint(float(sb));
-  o.level_q = mean + uint32_t(int(rc));
-  o.resid_q2 = mq >= 4294967294.0 ? 0xFFFFFFFEu : uint32_t(mq);
-  o.flat = o.resid_q2 <= a.max_spread_q2 && sa * sa + sb * sb <= a.max_tilt2 ? 1 : 0;
-  return o;
-}
-
 __global__ __launch_bounds__(kThreads) void k_slope_merge(const SlopeArgs a) {
   __shared__ unsigned long long sw[kSlopeWords][kThreads];
   __shared__ uint32_t sc[kThreads];
@@ -201,7 +159,7 @@ __global__ __launch_bounds__(kThreads) void k_slope_merge(const SlopeArgs a) {
     }
   }
   if (slice != 0 || cell >= n_cells) return;
-  const SlopeCell o = slope_cell_fit(a, cnt, s);
+  const SlopeCell o = slope_cell_fit(a.fit, cnt, s);   // (d2pc_sectors_slope_fit.hpp)
   if (a.count) a.count[cell] = cnt;
   if (a.sum) a.sum[cell] = s[0];
   if (a.sum2) a.sum2[cell] = s[1];
@@ -214,49 +172,17 @@ __global__ __launch_bounds__(kThreads) void k_slope_merge(const SlopeArgs a) {
   if (a.level_q) a.level_q[cell] = o.level_q;
   if (a.resid_q2) a.resid_q2[cell] = o.resid_q2;
   if (a.flat) a.flat[cell] = o.flat;
-  a.hand_on[cell] = cnt, a.hand_on[n_cells + cell] = o.level_q, a.hand_on[2 * n_cells + cell] = o.resid_q2;
-  uint8_t *bytes = reinterpret_cast<uint8_t *>(a.hand_on + 3 * size_t(n_cells));
-  bytes[cell] = o.flat, bytes[n_cells + cell] = o.fitted;
-}
-
-// ground_site_stage for the slope: the stage as it is, then the number of fitted cells over the summary's word 3 (the stage
-// stores 0 there from lane 0, which stores again here: one lane, program order).  fit_slot is the caller's, one word a wave,
-// filled before the call: the stage's first barrier publishes it.
-__device__ __forceinline__ void ground_site_stage(const GroundSiteStage &st, GroundSiteLds &lds, const uint32_t (&spread)[kGroundPerLane],
-                                                  uint32_t points, uint32_t n_flat, const uint32_t (&fit_slot)[kGroundSiteWaves]) {
-  ground_site_stage(st, lds, spread, points, n_flat);
-  if (st.summary && threadIdx.x == 0) {
-    uint32_t n_fit = 0;
-    for (int w = 0; w < kGroundSiteWaves; ++w) n_fit += fit_slot[w];
-    st.summary[3] = n_fit;
-  }
+  slope_hand_on(a.hand_on, n_cells, cell, cnt, o);
 }
 
 __global__ __launch_bounds__(kGroundSiteThreads) void k_slope_sites(const SlopeArgs a) {
   __shared__ GroundSiteLds lds;
   __shared__ uint32_t fit_slot[kGroundSiteWaves];
-  const int tid = int(threadIdx.x);
-  const int n_cells = a.grid.n_cells;
-  const uint8_t *flat_g = reinterpret_cast<const uint8_t *>(a.hand_on + 3 * size_t(n_cells));
-  uint32_t points = 0, n_flat = 0, n_fit = 0;
-  uint32_t resid[kGroundPerLane] = {};
-#pragma unroll
-  for (int k = 0; k < kGroundPerLane; ++k) {
-    const int c = tid + k * kGroundSiteThreads;
-    if (c >= n_cells) continue;
-    const uint8_t f = flat_g[c];
-    points += a.hand_on[c], n_flat += f, n_fit += flat_g[n_cells + c];
-    lds.mean_q[c] = int(a.hand_on[n_cells + c]), lds.flat[c] = f;
-    resid[k] = a.hand_on[2 * n_cells + c];
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) n_fit += uint32_t(__shfl_xor(int(n_fit), m, 64));
-  if ((tid & 63) == 0) fit_slot[tid >> 6] = n_fit;
   GroundSiteStage st;
   st.grid = a.grid, st.n_candidates = a.n_candidates;
   st.goal_i = reinterpret_cast<const uint32_t *>(a.step)[15], st.goal_j = reinterpret_cast<const uint32_t *>(a.step)[16];
   st.allowed = a.allowed, st.site = a.site, st.candidates = a.candidates, st.summary = a.summary;
-  ground_site_stage(st, lds, resid, points, n_flat, fit_slot);
+  slope_sites_from_hand_on(a.hand_on, st, lds, fit_slot);   // (d2pc_sectors_slope_fit.hpp)
 }
 
 }  // namespace
@@ -285,8 +211,7 @@ int launch_slope(const SlopeLaunch &in) {
   a.flip_a = g.flip[0], a.flip_b = g.flip[1], a.flip_h = g.flip[2];
   a.inv_c = g.inv_c, a.inv_q = g.inv_q;
   a.sub = float(in.plan.sub), a.sub_less_1 = in.plan.sub - 1;
-  a.min_fit = g.min_count > 3u ? g.min_count : 3u, a.max_spread_q2 = g.max_spread_q2;
-  a.scale = in.plan.scale, a.max_tilt2 = in.plan.max_tilt2;
+  a.fit = slope_fit_of(in.plan);
   hipStream_t s = static_cast<hipStream_t>(in.stream);
   void *args[] = {&a};
   (void)hipLaunchKernel(reinterpret_cast<const void *>(&k_slope_reduce), dim3(unsigned(in.blocks)), dim3(kThreads), args, in.plan.lds_bytes, s);

@@ -19,7 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "d2pc_sectors_ground_sites.hpp"
-#include "d2pc_sectors_terrain_plan.hpp"
+#include "d2pc_sectors_terrain_ring.hpp"
 
 namespace d2pc {
 namespace sectors {
@@ -93,43 +93,21 @@ __global__ __launch_bounds__(kGroundSiteThreads) void k_terrain_update(const Ter
   const int tid = int(threadIdx.x);
   const int n_cells = a.grid.n_cells, n_a = a.grid.n_a, n_b = a.grid.n_b, depth = a.depth;
   if (tid < depth) hdr[tid] = a.headers[tid];
-  // ---- 1. the anchor: the same words in every lane
-  const uint32_t h0_bits = a.step[14];
-  const float a0 = __uint_as_float(a.step[12]), b0 = __uint_as_float(a.step[13]), h0 = __uint_as_float(h0_bits);
-  const float ua = a0 * a.inv_c, ub = b0 * a.inv_c;
-  const bool anchored = fabsf(ua) <= kTerrainAnchorMax && fabsf(ub) <= kTerrainAnchorMax;   // (a NaN fails)
-  const int ia0 = anchored ? int(rintf(ua)) : 0, jb0 = anchored ? int(rintf(ub)) : 0;       // half to even
+  // ---- 1. the anchor: the same words in every lane (steps 1, 3 and 4 are d2pc_sectors_terrain_ring.hpp's)
+  const TerrainAnchor an = terrain_anchor(a.step, a.inv_c);
+  const uint32_t h0_bits = an.h0_bits;
+  const bool anchored = an.anchored;
+  const int ia0 = an.ia0, jb0 = an.jb0;
   __syncthreads();   // every read of a header in device memory lies before this barrier
 
   // ---- 3. the slot choice, identically in every lane
-  uint32_t largest = 0u, smallest = 0xFFFFFFFFu;
-  int v = 0;
-  for (int s = 0; s < depth; ++s) {
-    const uint32_t seq = hdr[s].w;
-    largest = seq > largest ? seq : largest;
-    if (seq < smallest) smallest = seq, v = s;   // (the lowest index on a tie)
-  }
-  const bool restart = largest == 0xFFFFFFFFu;   // all slots are first taken as empty
-  v = restart ? 0 : v;
-  const uint32_t q = restart ? 1u : largest + 1u;
+  const TerrainSlot sl = terrain_slot_choice(hdr, depth);
+  const uint32_t largest = sl.largest, q = sl.q;
+  const bool restart = sl.restart;
+  const int v = sl.v;
 
   // ---- 4. the slots that take part, compacted by wave 0 (all 64 lanes of it are here: the ballot is whole)
-  if (tid < 64) {
-    bool takes = false;
-    long long di = 0, dj = 0;
-    if (anchored && !restart && tid < depth && tid != v) {
-      const uint4 h = hdr[tid];
-      di = static_cast<long long>(ia0) - static_cast<long long>(int(h.x));
-      dj = static_cast<long long>(jb0) - static_cast<long long>(int(h.y));
-      takes = h.w != 0u && __uint_as_float(h.z) == h0 && di > -n_a && di < n_a && dj > -n_b && dj < n_b;
-    }
-    const unsigned long long m = __ballot(takes);
-    if (takes) {
-      const int pos = __popcll(m & ((1ull << tid) - 1ull));   // (< 15: at most depth - 1 lanes take)
-      part_slot[pos] = tid, part_di[pos] = int(di), part_dj[pos] = int(dj);
-    }
-    if (tid == 0) part_n = __popcll(m);
-  }
+  if (tid < 64) terrain_participants(hdr, depth, n_a, n_b, an, sl, tid, part_slot, part_di, part_dj, &part_n);
   __syncthreads();
   const int n_part = part_n;
 

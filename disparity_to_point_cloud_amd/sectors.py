@@ -37,6 +37,9 @@ SECTORS_SYMBOLS = [
     "d2pc_sectors_slope_config_init", "d2pc_sectors_slope_geometry", "d2pc_sectors_slope_of_degrees", "d2pc_sectors_slope_create",
     "d2pc_sectors_slope_destroy", "d2pc_sectors_slope_last_error", "d2pc_sectors_slope_blocks", "d2pc_sectors_slope_desc_init",
     "d2pc_sectors_slope_desc_check", "d2pc_sectors_slope_process_device",
+    "d2pc_sectors_relief_geometry", "d2pc_sectors_relief_create", "d2pc_sectors_relief_destroy", "d2pc_sectors_relief_last_error",
+    "d2pc_sectors_relief_state", "d2pc_sectors_relief_reset_device", "d2pc_sectors_relief_desc_init", "d2pc_sectors_relief_desc_check",
+    "d2pc_sectors_relief_update_device",
 ]
 EMPTY_AGE, OLDEST_AGE = 0xFFFFFFFF, 0xFFFFFFFE   # the age word of an empty record; where an age saturates
 STEER_MAX_REACH_SECTORS, STEER_MAX_REACH_LAYERS, STEER_MAX_CANDIDATES, STEER_MAX_WEIGHT = 32, 16, 32, 4095
@@ -205,6 +208,25 @@ class SectorsSlopeDesc(ctypes.Structure):
     ]
 
 
+class SectorsReliefGeometry(ctypes.Structure):
+    _fields_ = [
+        ("n_cells", ctypes.c_int32), ("inv_c", ctypes.c_float), ("slot_bytes", ctypes.c_size_t), ("state_bytes", ctypes.c_size_t),
+        ("headers_offset", ctypes.c_size_t), ("tables_offset", ctypes.c_size_t), ("scale", ctypes.c_double), ("max_tilt2", ctypes.c_double),
+        ("blocks", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5),
+    ]
+
+
+class SectorsReliefDesc(ctypes.Structure):
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("n_candidates", ctypes.c_int32), ("step", ctypes.c_void_p), ("frame_count", ctypes.c_void_p),
+        ("frame_sum", ctypes.c_void_p), ("frame_sum2", ctypes.c_void_p), ("frame_moments", ctypes.c_void_p), ("allowed", ctypes.c_void_p),
+        ("count", ctypes.c_void_p), ("sum", ctypes.c_void_p), ("sum2", ctypes.c_void_p), ("moments", ctypes.c_void_p),
+        ("slope_a", ctypes.c_void_p), ("slope_b", ctypes.c_void_p), ("level_q", ctypes.c_void_p), ("resid_q2", ctypes.c_void_p),
+        ("flat", ctypes.c_void_p), ("site", ctypes.c_void_p), ("candidates", ctypes.c_void_p), ("summary", ctypes.c_void_p),
+        ("status", ctypes.c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -320,6 +342,20 @@ def load_sectors_library(variant=None):
         L.d2pc_sectors_slope_desc_init.restype = None
         L.d2pc_sectors_slope_desc_check.argtypes = [gcfg, scfg, sdesc]
         L.d2pc_sectors_slope_process_device.argtypes = [vp, sdesc, vp]
+    if variant is None or hasattr(L, "d2pc_sectors_relief_create"):   # (an A/B variant may be a build from before the relief)
+        gcfg, scfg, tcfg = ctypes.POINTER(SectorsGroundConfig), ctypes.POINTER(SectorsSlopeConfig), ctypes.POINTER(SectorsTerrainConfig)
+        rdesc = ctypes.POINTER(SectorsReliefDesc)
+        L.d2pc_sectors_relief_geometry.argtypes = [gcfg, scfg, tcfg, ctypes.POINTER(SectorsReliefGeometry)]
+        L.d2pc_sectors_relief_create.argtypes = [gcfg, scfg, tcfg, ctypes.POINTER(vp)]
+        L.d2pc_sectors_relief_destroy.argtypes = [vp]
+        L.d2pc_sectors_relief_last_error.argtypes = [vp]
+        L.d2pc_sectors_relief_last_error.restype = ctypes.c_char_p
+        L.d2pc_sectors_relief_state.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
+        L.d2pc_sectors_relief_reset_device.argtypes = [vp, vp]
+        L.d2pc_sectors_relief_desc_init.argtypes = [rdesc]
+        L.d2pc_sectors_relief_desc_init.restype = None
+        L.d2pc_sectors_relief_desc_check.argtypes = [gcfg, scfg, tcfg, rdesc]
+        L.d2pc_sectors_relief_update_device.argtypes = [vp, rdesc, vp]
     if variant is None:
         _lib = L
     return L
@@ -826,3 +862,80 @@ class SectorsSlope(_Session):
             count=_ptr(count), sum=_ptr(sum), sum2=_ptr(sum2), moments=_ptr(moments), slope_a=_ptr(slope_a), slope_b=_ptr(slope_b),
             level_q=_ptr(level_q), resid_q2=_ptr(resid_q2), flat=_ptr(flat), site=_ptr(site), candidates=_ptr(candidates),
             summary=_ptr(summary)), stream_ptr)
+
+
+def sectors_relief_desc_init(**kw) -> SectorsReliefDesc:
+    """d2pc_sectors_relief_desc_init, then the given fields."""
+    d = SectorsReliefDesc()
+    load_sectors_library().d2pc_sectors_relief_desc_init(ctypes.byref(d))
+    return _set(d, kw)
+
+
+def sectors_relief_geometry(gcfg: SectorsGroundConfig, scfg: SectorsSlopeConfig, tcfg: SectorsTerrainConfig) -> SectorsReliefGeometry:
+    """d2pc_sectors_relief_geometry (host arithmetic); raises D2pcError as the C function refuses."""
+    g = SectorsReliefGeometry()
+    st = load_sectors_library().d2pc_sectors_relief_geometry(ctypes.byref(gcfg), ctypes.byref(scfg), ctypes.byref(tcfg), ctypes.byref(g))
+    if st != 0:
+        raise D2pcError(st, "sectors_relief_geometry(%d x %d, sub %d, depth %d)" % (gcfg.n_a, gcfg.n_b, scfg.sub, tcfg.depth))
+    return g
+
+
+def sectors_relief_desc_check(gcfg: SectorsGroundConfig, scfg: SectorsSlopeConfig, tcfg: SectorsTerrainConfig, desc: SectorsReliefDesc) -> int:
+    """d2pc_sectors_relief_desc_check: the status d2pc_sectors_relief_update_device would refuse `desc` with (0: accepted)."""
+    return load_sectors_library().d2pc_sectors_relief_desc_check(ctypes.byref(gcfg), ctypes.byref(scfg), ctypes.byref(tcfg), ctypes.byref(desc))
+
+
+class SectorsRelief(_Session):
+    """d2pc_sectors_relief_*: the slope's per-cell tables (count and nine sums) of the last `depth` frames, kept on the device,
+    and the plane fit, the landing grid and the ranked sites of that scrolling window in two launches.  `update` takes torch
+    tensors or raw device pointers, is asynchronous on `stream` and allocates nothing."""
+
+    _PREFIX = "d2pc_sectors_relief"
+
+    def __init__(self, gcfg: SectorsGroundConfig, scfg: SectorsSlopeConfig = None, tcfg: SectorsTerrainConfig = None, variant=None, **kw):
+        self.cfg = gcfg
+        self.scfg = scfg if scfg is not None else sectors_slope_config_init()
+        self.tcfg = _set(tcfg, kw) if tcfg is not None else sectors_terrain_config_init(**kw)
+        self._create(variant, "sectors_relief_create(%d x %d, sub %d, depth %d)" % (gcfg.n_a, gcfg.n_b, self.scfg.sub, self.tcfg.depth),
+                     ctypes.byref(self.cfg), ctypes.byref(self.scfg), ctypes.byref(self.tcfg))
+        self.geometry = sectors_relief_geometry(self.cfg, self.scfg, self.tcfg)
+        self.n_cells, self.depth, self.blocks = self.geometry.n_cells, self.tcfg.depth, self.geometry.blocks
+
+    def state(self):
+        """d2pc_sectors_relief_state: (the state block's device pointer, its bytes)."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        st = self._L.d2pc_sectors_relief_state(self._h, ctypes.byref(p), ctypes.byref(n))
+        if st:
+            raise D2pcError(st, self.last_error())
+        return p.value, n.value
+
+    def state_tensor(self):
+        """The state block as a torch uint8 tensor that VIEWS it (the CUDA array interface, no copy): `.clone()` saves a map and
+        `.copy_()` restores one, in stream order with the updates.  The view must not outlive the session."""
+        import torch
+
+        ptr, n = self.state()
+        return torch.as_tensor(_StateView(ptr, n), device="cuda:%d" % self.cfg.device_id)
+
+    def update_desc(self, desc: SectorsReliefDesc, stream_ptr=None):
+        """d2pc_sectors_relief_update_device."""
+        st = self._L.d2pc_sectors_relief_update_device(self._h, ctypes.byref(desc), stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())
+
+    def update(self, step, frame_count, frame_sum, frame_sum2, frame_moments, allowed=None, count=None, sum=None, sum2=None, moments=None,
+               slope_a=None, slope_b=None, level_q=None, resid_q2=None, flat=None, site=None, candidates=None, n_candidates=1,
+               summary=None, status=None, stream_ptr=None):
+        """The descriptor from tensors (their data_ptr) or raw device pointers, then the call."""
+        self.update_desc(sectors_relief_desc_init(
+            n_candidates=n_candidates, step=_ptr(step), frame_count=_ptr(frame_count), frame_sum=_ptr(frame_sum),
+            frame_sum2=_ptr(frame_sum2), frame_moments=_ptr(frame_moments), allowed=_ptr(allowed), count=_ptr(count), sum=_ptr(sum),
+            sum2=_ptr(sum2), moments=_ptr(moments), slope_a=_ptr(slope_a), slope_b=_ptr(slope_b), level_q=_ptr(level_q),
+            resid_q2=_ptr(resid_q2), flat=_ptr(flat), site=_ptr(site), candidates=_ptr(candidates), summary=_ptr(summary),
+            status=_ptr(status)), stream_ptr)
+
+    def reset(self, stream_ptr=None):
+        """d2pc_sectors_relief_reset_device."""
+        st = self._L.d2pc_sectors_relief_reset_device(self._h, stream_ptr)
+        if st:
+            raise D2pcError(st, self.last_error())

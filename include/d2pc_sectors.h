@@ -321,6 +321,46 @@
  *                sa = gu * scale, sb = gw * scale
  *     site, candidates, summary   the GROUND block's, word for word, with level_q for mean_q, resid_q2 for spread_q2 and
  *                this flat for the ground's; summary word 3 is the number of fitted cells
+ *
+ * ------------------------------------------------------------------------------------- RELIEF (d2pc_sectors_relief_*)
+ * The terrain remembers and scrolls, but judges a cell by spread_q2 alone; the slope tells a tilted cell from a rough one,
+ * but sees one call's clouds only, and a cell that a frame covers with a sliver is not fitted and is lost at the next frame.
+ * The relief session is the two joined: it keeps the slope's per-cell tables (count and the nine 64-bit sums) of the last
+ * `depth` frames on the device, each with the world cell index of its grid's corner, and
+ * d2pc_sectors_relief_update_device -- two launches behind d2pc_sectors_slope_process_device -- stores the new frame's
+ * tables, sums the window as seen from the new corner and forms the SLOPE block's fit, per-cell outputs, sites, cost,
+ * candidates and summary from the window's ten sums.  u and w are positions INSIDE a cell: a scroll by whole cells does not
+ * change them, so a stored table is read at a shifted index and added as it is.  The sums are of integers: for tables that
+ * slope calls of the same two configurations wrote, with the caller keeping the corner on a multiple of the cell size, the
+ * result is the same bytes as ONE slope call over all the window's clouds.  It takes the ground's and the slope's
+ * configurations unchanged and the terrain's d2pc_sectors_terrain_config (depth) beside them.
+ * tests/sectors_relief_ref.py restates it in numpy and Python integers.
+ *
+ * State (d2pc_sectors_relief_state: one block of device memory, little-endian; two copies save and restore a map).
+ *     16 headers of 16 bytes at offset 0, exactly the terrain's:  {int32 ia0, int32 jb0, float h0, uint32 seq}.  seq 0 means
+ *     empty; the headers at and beyond `depth` stay zero.  Then, from byte 256, `depth` tables of slot_bytes = 76 * n_cells
+ *     rounded up to a multiple of 16; table s belongs to header s and holds nine 64-bit planes of n_cells entries each --
+ *     sum, sum2, su, sw, suu, suw, sww, suk, swk, in this order -- and then count[n_cells] (uint32): the slope slab's layout.
+ *
+ * The update, from the step (the very one the slope call used: a0, b0, h0, goal_i, goal_j are read) and the frame's count,
+ * sum, sum2 and moments (su .. swk, plane after plane) as d2pc_sectors_slope_process_device wrote them.
+ *     1 .. 4 and 6.  Steps 1, 2, 3, 4 and 6 of the TERRAIN block, word for word, with the ten sums in place of the three:
+ *        the anchor at 2^29 and half to even; a frame that is not anchored leaves the state untouched; the replaced slot v,
+ *        q and the restart at 0xFFFFFFFF; slot v becomes {ia0, jb0, h0, q} and a copy of the frame's ten tables (sum, sum2
+ *        and the seven moments into the nine planes in the order above, then count); the window of cell (i, j) is the
+ *        frame's entry plus the entry at (i + ia0 - ia0_s, j + jb0 - jb0_s) of every other slot s with seq != 0 and h0_s ==
+ *        h0 (float ==), where that lies inside the grid, the differences formed in 64 bits; count adds modulo 2^32, each
+ *        of the nine 64-bit sums modulo 2^64; status = {q, the slots that took part (the frame included), (uint32)ia0,
+ *        (uint32)jb0}.
+ *     5. Every output but status is the SLOPE block's "Fit", "Outputs" and its sites, cost, candidates and summary, word
+ *        for word, applied to the window's count and nine sums: count, sum, sum2 and moments are the window's; min_count,
+ *        max_spread_q2, max_slope, max_step_q, window, the weights and rough_cap now judge the WINDOW's cells; the goal
+ *        cell is relative to the current corner; summary word 3 is the number of fitted window cells.
+ *     Not anchored: every per-cell output is that of an empty window (count, sum, sum2 and moments 0, slope_a and slope_b
+ *     0x7FC00000, level_q 0x80000000, resid_q2 0xFFFFFFFF, flat 0, site 0), the candidates are all ones, the summary is
+ *     zeros and status = {the largest seq of headers 0 .. depth - 1, 0, 0, 0}.
+ *     The guarantee holds for tables that slope calls wrote.  For other tables the per-cell outputs follow the wrapping
+ *     formulas and the fit's double sequence, and site / candidates are unspecified.
  */
 #ifndef D2PC_SECTORS_H
 #define D2PC_SECTORS_H
@@ -867,6 +907,82 @@ int d2pc_sectors_slope_desc_check(const d2pc_sectors_ground_config *gcfg, const 
  * The slabs belong to the session: one call of a session in flight per stream order; two streams need two sessions.
  */
 int d2pc_sectors_slope_process_device(d2pc_sectors_slope *s, const d2pc_sectors_slope_desc *desc, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------- the relief */
+typedef struct d2pc_sectors_relief_geometry_t {
+  int32_t n_cells;             /* n_a * n_b */
+  float inv_c;                 /* as the specification forms it: the anchor's factor */
+  size_t slot_bytes;           /* one stored table: 76 * n_cells rounded up to a multiple of 16 */
+  size_t state_bytes;          /* the state block: 256 + depth * slot_bytes */
+  size_t headers_offset;       /* 0 */
+  size_t tables_offset;        /* 256: table s begins at tables_offset + s * slot_bytes */
+  double scale, max_tilt2;     /* the slope's, as the specification forms them */
+  int32_t blocks;              /* of the window launch: 16 cells each */
+  int32_t reserved[5];
+} d2pc_sectors_relief_geometry_t;
+/* Host arithmetic only, no device.  A NULL `out` is D2PC_ERR_INVALID_ARG before everything.  First the refusals of
+ * d2pc_sectors_slope_geometry for `gcfg` and `scfg`, unchanged and in its order (the ground's, the slope's, more than 2,155
+ * cells); then those of `tcfg` as d2pc_sectors_terrain_geometry lists them: D2PC_ERR_INVALID_ARG: a NULL tcfg, its
+ * struct_size;  D2PC_ERR_BAD_SIZE: depth outside 1 .. 16;  D2PC_ERR_INVALID_ARG: a reserved word that is not zero. */
+int d2pc_sectors_relief_geometry(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_slope_config *scfg,
+                                 const d2pc_sectors_terrain_config *tcfg, d2pc_sectors_relief_geometry_t *out);
+
+typedef struct d2pc_sectors_relief d2pc_sectors_relief;
+/* `gcfg` and `scfg` are the configurations the slope session was made from: min_count, max_spread_q2, max_slope, max_step_q,
+ * window, the weights and rough_cap now apply to the WINDOW's cells.  Allocates the state once, with every header zero, and
+ * 14 bytes per cell that the two launches hand on.  D2PC_ERR_NO_DEVICE without a GPU or for a device_id that is none. */
+int d2pc_sectors_relief_create(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_slope_config *scfg,
+                               const d2pc_sectors_terrain_config *tcfg, d2pc_sectors_relief **out);
+int d2pc_sectors_relief_destroy(d2pc_sectors_relief *r);
+/* The message of the session's last refusal or failure ("null session" for NULL). */
+const char *d2pc_sectors_relief_last_error(const d2pc_sectors_relief *r);
+/* The state block in DEVICE memory and its size (each nullable), laid out as the RELIEF block documents: a caller saves and
+ * restores a map with one copy each way, in stream order with the updates. */
+int d2pc_sectors_relief_state(const d2pc_sectors_relief *r, void **device_ptr, size_t *bytes);
+/* Asynchronous on `stream`: one small launch that zeroes the 16 headers with vector stores (the window is empty again;
+ * the tables are left as they are, nothing reads a table of an empty header). */
+int d2pc_sectors_relief_reset_device(d2pc_sectors_relief *r, void *stream);
+
+typedef struct d2pc_sectors_relief_desc {
+  uint32_t struct_size;        /* sizeof(d2pc_sectors_relief_desc) */
+  int32_t n_candidates;        /* 1 .. 32 when `candidates` is given */
+  const d2pc_sectors_ground_step *step;   /* DEVICE, 4-byte aligned: the very step the slope call used */
+  const uint32_t *frame_count; /* DEVICE in, all four required: as d2pc_sectors_slope_process_device wrote them */
+  const int64_t *frame_sum;    /*   (count, sum, sum2: n_cells entries each; moments: 7 x n_cells); */
+  const uint64_t *frame_sum2;  /*   frame_sum, frame_sum2 and frame_moments 8-byte aligned */
+  const int64_t *frame_moments;
+  const uint8_t *allowed;      /* DEVICE, nullable: one byte per cell, zero = no site */
+  uint32_t *count;             /* DEVICE out, the WINDOW's, each nullable; at least one of these thirteen is given */
+  int64_t *sum;                /* 8-byte aligned */
+  uint64_t *sum2;              /* 8-byte aligned */
+  int64_t *moments;            /* 7 x n_cells, 8-byte aligned */
+  float *slope_a, *slope_b;
+  int32_t *level_q;
+  uint32_t *resid_q2;
+  uint8_t *flat;
+  uint8_t *site;
+  d2pc_sectors_ground_candidate *candidates;   /* n_candidates records, 8-byte aligned */
+  uint32_t *summary;           /* 4 words */
+  uint32_t *status;            /* 4 words: {seq, slots that took part, (uint32)ia0, (uint32)jb0} */
+} d2pc_sectors_relief_desc;
+/* struct_size, n_candidates 1; everything else zero. */
+void d2pc_sectors_relief_desc_init(d2pc_sectors_relief_desc *desc);
+/* Host only: what d2pc_sectors_relief_update_device refuses of `desc` for a session of the three configurations, without a
+ * session; first the refusals of the configurations as d2pc_sectors_relief_geometry makes them.  D2PC_ERR_INVALID_ARG: NULL,
+ * struct_size, a NULL step, frame_count, frame_sum, frame_sum2 or frame_moments, no output, n_candidates out of 1 .. 32 when
+ * candidates is given, a pointer not aligned to its type (8 bytes for frame_sum, frame_sum2, frame_moments, sum, sum2,
+ * moments and candidates), an output that overlaps step, a frame table, allowed or another output.  The session adds one
+ * refusal: a buffer that overlaps its own state block. */
+int d2pc_sectors_relief_desc_check(const d2pc_sectors_ground_config *gcfg, const d2pc_sectors_slope_config *scfg,
+                                   const d2pc_sectors_terrain_config *tcfg, const d2pc_sectors_relief_desc *desc);
+/*
+ * Asynchronous on `stream` (NULL = the HIP default stream): TWO launches -- the window and the fit in many blocks, then one
+ * block that commits the header, writes status and ranks the sites --, no global atomic, no memset, no allocation, no host
+ * read: it can be captured into a graph behind d2pc_sectors_slope_process_device.  Every refusal is made before anything is
+ * enqueued.  Bit-reproducible: every sum is of integers, the fit is one fixed sequence of double operations per cell and
+ * every minimum is of distinct keys.  The state belongs to the session: one update of a session in flight per stream order.
+ */
+int d2pc_sectors_relief_update_device(d2pc_sectors_relief *r, const d2pc_sectors_relief_desc *desc, void *stream);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,11 @@ ranks them).  GPU box only.
                                             one-camera frame and the rig's merged cloud, in producer order and shuffled, in ONE interleaved
                                             run.  No time is fixed in advance: L is read against G and C of its row; L0 - G0 is what the
                                             larger slabs cost, (L - L0) - (G - G0) what the seven more adds a record cost
+  python tools/sectors_bench.py --relief
+                                        ->  profiles/sectors_relief_bench.txt: the relief's update (d2pc_sectors_relief_update_device, two launches,
+                                            stored tables of 76 bytes a cell) alone at 16 x 16 x 8 and 46 x 46 x 16, with every slot of the window
+                                            taking part and with none, beside the slope call's L and L0, the terrain's update of the same grid and
+                                            depth and a copy of the bytes the update reads, in ONE interleaved run.  No time is fixed in advance
 """
 import argparse
 import os
@@ -979,6 +984,109 @@ def terrain(a):
     return lines
 
 
+RELIEF_GRIDS = [(dict(n_a=16, n_b=16, cell_size=0.5), 8), (dict(n_a=46, n_b=46, cell_size=0.125), 16)]   # (grid, depth)
+
+
+def relief(a):
+    """The relief's update alone beside the slope call that feeds it, the terrain's update at the same grid and depth and a
+    copy of the bytes the update reads, on one cloud, in one run."""
+    prop = torch.cuda.get_device_properties(0)
+    size = os.path.getsize(d2pc.sectors_library_path())
+    lines = ["# tools/sectors_bench.py --relief --rounds %d --iters %d" % (a.rounds, a.iters),
+             "# device draw: %s, %d CUs (one device, one process, ONE run; every arm of this file interleaved round by round); libd2pc_sectors.so is %d bytes" % (
+                 prop.name, prop.multi_processor_count, size),
+             "# the cloud is tools/sectors_bench.py --ground's one-camera frame (a level ground under a nadir camera, 30 % holes) in producer order; the",
+             "# grid lies under the camera, quantum 0.002, sub 8, max_slope tan 15 deg, every output with 5 candidates (and status).",
+             "# L = d2pc_sectors_slope_process_device alone (three launches); L0 = the same call with a count of 0: the slope's fixed part;",
+             "# R all = d2pc_sectors_relief_update_device alone (TWO launches: the window and the fit in n_cells / 16 blocks, then one block) on L's count /",
+             "# sum / sum2 / moments with the corner held, so every slot of the window takes part (depth - 1 stored tables of 76 bytes a cell are read whole);",
+             "# R none = the same with a NaN h0 in the step: the frame is anchored and stored, no stored table matches it, the window is the frame alone;",
+             "# T all = d2pc_sectors_terrain_update_device (ONE launch of one block, 20 bytes a cell) of the same grid and depth on L's count / sum / sum2,",
+             "# every slot taking part; C = d2pc_membench_copy moving `read` bytes = depth x 76 x n_cells, what R all reads of tables (the frame's and the",
+             "# stored).  GB/s = the bytes of the depth - 1 stored tables over the WHOLE of R all, both launches' fixed parts included: a lower bound on the",
+             "# window launch's rate (R all - R none, the column before it, can lie inside the run's spread).  us per call: median (min .. max) over the rounds.",
+             "# No time was fixed in advance",
+             "%-34s %9s %5s %9s %-30s %-30s %-30s %-30s %-30s %-30s %7s %7s %7s %7s %7s %7s" % (
+                 "cloud, grid x depth", "records", "took", "read", "R all", "R none", "L", "L0", "T all", "C", "Rall/C", "Rall/L0", "Rall/T", "Rnon/L0", "Ra-Rn", "GB/s")]
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    s = torch.cuda.current_stream().cuda_stream
+    name, n, w, h, mode, rig_case, holes = CASES[0]
+    with d2pc.Context(q=d2pc.make_q(), border=BORDER, mode=mode) as ctx:
+        prod = Producer(ctx, n, w, h, rig_case, holes, gen)
+        npts, cloud, corner = level_ground(ctx, prod, gen, s)
+        step = ground_step(corner)
+        lone = torch.from_numpy(d2pc.sectors_ground_step(NADIR, [0.0, 0.0, 10.0], corner[:2] + [np.nan], 8, 8).view(np.int32).copy()).to("cuda")
+        count = torch.tensor([npts], dtype=torch.int32, device="cuda")
+        zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+        rows, arms, keep = [], [], []
+        for grid, depth in RELIEF_GRIDS:
+            slp = d2pc.SectorsSlope(d2pc.sectors_ground_config_init(**ground_grid(grid, prod)))
+            nc = slp.n_cells
+            lo, l0, r_all, r_none = [slope_outputs(nc, 5) for _ in range(4)]
+            t_all = ground_outputs(nc, 5)
+            status = [torch.zeros(4, dtype=torch.int32, device="cuda") for _ in range(3)]
+            rel = [d2pc.SectorsRelief(slp.cfg, slp.scfg, depth=depth) for _ in range(2)]   # a window each: the two arms do not disturb each other
+            ter = d2pc.SectorsTerrain(slp.cfg, depth=depth)
+            wide = os.path.exists(d2pc.sectors_library_path("relief64"))   # `make sectors SNAME=relief64 SDEFS=-DD2PC_SECTORS_RELIEF_CELLS=64`
+            if wide:
+                rel.append(d2pc.SectorsRelief(slp.cfg, slp.scfg, depth=depth, variant="relief64"))
+                r_wide, status = slope_outputs(nc, 5), status + [torch.zeros(4, dtype=torch.int32, device="cuda")]
+            read = depth * 76 * nc
+            src, dst = torch.empty(read, dtype=torch.uint8, device="cuda"), torch.empty(read, dtype=torch.uint8, device="cuda")
+            keep.append((slp, rel, ter, lo, l0, r_all, r_none, t_all, status, src, dst))
+            slp.process(cloud, npts, step, counts=count, n_candidates=5, stream_ptr=s, **lo)
+
+            def update(r, st_step, o, st_, lo=lo):
+                return lambda: r.update(st_step, lo["count"], lo["sum"], lo["sum2"], lo["moments"], n_candidates=5, status=st_, stream_ptr=s, **o)
+
+            def update_terrain(lo=lo, t_all=t_all, st_=status[2], ter=ter):
+                ter.update(step, lo["count"], lo["sum"], lo["sum2"], n_candidates=5, status=st_, stream_ptr=s, **t_all)
+
+            arms += [update(rel[0], step, r_all, status[0]), update(rel[1], lone, r_none, status[1]),
+                     lambda slp=slp, lo=lo: slp.process(cloud, npts, step, counts=count, n_candidates=5, stream_ptr=s, **lo),
+                     lambda slp=slp, l0=l0: slp.process(cloud, npts, step, counts=zero, n_candidates=5, stream_ptr=s, **l0),
+                     update_terrain,
+                     lambda src=src, dst=dst, read=read: ctx.membench_copy(src.data_ptr(), dst.data_ptr(), read, s),
+                     update(rel[2], step, r_wide, status[3]) if wide else (lambda: None)]
+            rows.append(("%s, %d x %d x %d" % (name[:14].strip(), grid["n_a"], grid["n_b"], depth), depth, read, nc, status, lo, r_all))
+            if wide:
+                keep.append(r_wide)
+        for _ in range(20):   # warm-up: code objects, and more updates than the deepest window holds
+            for fn in arms:
+                fn()
+        torch.cuda.synchronize()
+        ctx.check_async_error()
+        for row, depth, read, nc, status, lo, r_all in rows:
+            took = [int(x.cpu().numpy().view(np.uint32)[1]) for x in status]
+            assert took == [depth, 1, depth] + [depth] * (len(status) - 3), "%s: %s slots took part" % (row, took)
+            assert torch.equal(r_all["count"], lo["count"] * depth) and torch.equal(r_all["moments"], lo["moments"] * depth), "the window is not depth frames"
+        iters = int(min(max(a.iters, 30000.0 / timed(arms[3], 5)), 4000))
+        t = interleaved(arms, a.rounds, iters)
+        ctx.check_async_error()
+        lines.insert(-1, "# %d calls per timed window" % iters)
+        for k, (row, depth, read, nc, status, lo, r_all) in enumerate(rows):
+            Ra, Rn, L, L0, Ta, C, Rw = t[7 * k:7 * k + 7]
+            m = [float(np.median(x)) for x in (Ra, Rn, L, L0, Ta, C)]
+            stored = (depth - 1) * 76 * nc
+            lines.append("%-34s %9d %5d %9d %-30s %-30s %-30s %-30s %-30s %-30s %7.2f %7.2f %7.2f %7.2f %7.1f %7.1f" % (
+                row, npts, depth, read, fmt(Ra), fmt(Rn), fmt(L), fmt(L0), fmt(Ta), fmt(C), m[0] / m[5], m[0] / m[3], m[0] / m[4], m[1] / m[3],
+                m[0] - m[1], stored / m[0] / 1000.0))
+            fs = tuple(int(v) for v in r_all["summary"].cpu().numpy().view(np.uint32))
+            lines.append("#   the window of %d frames: %d points, %d flat cells, %d sites, %d fitted of %d cells; %d blocks" % (depth, fs[0], fs[1], fs[2], fs[3], nc,
+                                                                                                                      (nc + 15) // 16))
+            if len(status) > 3:
+                lines.append("#   R all of the 64 cells x 4 slices build (libd2pc_sectors_relief64.so, %d blocks, four list entries a lane): %s" % ((nc + 63) // 64, fmt(Rw)))
+        for slp, rel, ter, *_ in [x for x in keep if isinstance(x, tuple)]:
+            for x in rel:
+                x.close()
+            ter.close()
+            slp.close()
+        prod.close()
+    for ln in lines:
+        print(ln, flush=True)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=9)
@@ -991,16 +1099,17 @@ def main():
     ap.add_argument("--ground", action="store_true", help="the landing grid beside the sectors call instead of the cost table")
     ap.add_argument("--terrain", action="store_true", help="the terrain's update beside the ground call and the steer call instead of the cost table")
     ap.add_argument("--slope", action="store_true", help="the plane fit per cell beside the ground call instead of the cost table")
+    ap.add_argument("--relief", action="store_true", help="the relief's update beside the slope call, the terrain's update and a copy instead of the cost table")
     ap.add_argument("--parent", default=None, help="libd2pc_sectors_<PARENT>.so, an earlier build: with --elevation beside the height rows; "
                     "alone, the table of this build against it (S, M, T, T32, G and the terrain's update)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.parent and (a.memory or a.ab or a.ground or a.terrain or a.slope):
+    if a.parent and (a.memory or a.ab or a.ground or a.terrain or a.slope or a.relief):
         ap.error("--parent goes with --elevation or --steer or stands alone (its own table holds the memory's rows)")
     versus = bool(a.parent) and not (a.memory or a.elevation or a.ab or a.steer)
-    if a.ground or a.terrain or a.slope:
-        lines = slope(a) if a.slope else terrain(a) if a.terrain else ground(a)
-        out = a.out or os.path.join(ROOT, "profiles", "sectors_slope_bench.txt" if a.slope else "sectors_terrain_bench.txt" if a.terrain else "sectors_ground_bench.txt")
+    if a.ground or a.terrain or a.slope or a.relief:
+        lines = relief(a) if a.relief else slope(a) if a.slope else terrain(a) if a.terrain else ground(a)
+        out = a.out or os.path.join(ROOT, "profiles", "sectors_relief_bench.txt" if a.relief else "sectors_slope_bench.txt" if a.slope else "sectors_terrain_bench.txt" if a.terrain else "sectors_ground_bench.txt")
         with open(out, "w") as f:
             f.write("\n".join(lines) + "\n")
         print("wrote", out)
